@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — HydraVox-CV3 speech-synthesis hot path on MI355X (BASELINE.json metric / config).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): HydraVox-CV3, inference_head_num=2, batch = 8 x 512-char utterances
@@ -13,6 +13,11 @@ One step = one batch through llm -> flow -> hift.  N > 1: weak scaling, every ra
 
 `value` = speech tokens per second of the whole job (all stages, all ranks); the reference's own per-stage figures
 (TPS = tokens / LLM wall, RTF = wall / audio seconds; infer_speech_model.py:563-565, 594-604) ride along as extra keys.
+
+A plain run sets up, warms up (W steps of the schedule the timed steps run), times K steps and prints the line.  Everything else the line
+can carry — the strict-batch step, the decode grid alone, the per-kernel profiling step, single_request / head_sweep / bf16_id_agreement, the
+fp32 / ids-exact / exact-vocoder modes, the other BASELINE configs and the CPU baseline — runs only with --full.  --dump-outputs DIR writes
+what the timed path returned in its last step as .npy files (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -51,6 +56,9 @@ def parse():
     ap.add_argument('--streams', type=int, default=64, help='(--config acoustic) pre-tokenised speech-token streams per GPU, lengths U{352..2816}')
     ap.add_argument('--tiny', action='store_true', help='toy dimensions (plumbing check only; INVALID as a benchmark)')
     ap.add_argument('--llm-dtype', choices=['bf16', 'fp32'], default='bf16', help='fp32: the speech-token LM on the exact fp32 forms (ids bit-exact against the reference) with the flow decoder / vocoder as in the headline')
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline as well: the strict-batch step, the decode grid alone, the per-kernel profiling '
+                    'step, the extras, the fp32 / ids-exact / exact-vocoder modes, the other configs and the CPU baseline (the --no-* options below switch parts of it off)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the timed path returned in its last step to DIR/*.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-fp32-mode', action='store_true', help='skip the extra, untimed step in the parity-exact fp32 mode (the `fp32_mode` object of the line)')
     ap.add_argument('--lm-slots', type=int, default=0, help='sequences decoded in one grid (continuous batching): utterances of later steps join as earlier ones finish; '
@@ -75,7 +83,44 @@ def parse():
     ap.add_argument('--lib-opt', action='append', default=[], metavar='NAME=VALUE', help='library option(s) set before anything runs (hvx_set_option; A / B runs, e.g. attn_dit_form=16 = the round-5 attention tile); recorded in config.lib_options')
     ap.add_argument('--cpu-baseline-worker', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--stub-pipeline', action='store_true', help=argparse.SUPPRESS)      # plumbing check of the rank logic on CPU / gloo (tools/bench_stub.py); INVALID as a benchmark
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not args.full:
+        args.no_cpu_baseline = args.no_fp32_mode = args.no_extras = True
+        args.config_steps = 0
+    return args
+
+
+DUMP_WAVE_VALUES = 1 << 22           # waveform samples --dump-outputs writes over all utterances of the step (16 MB of float32 + their positions)
+
+
+def dump_outputs(out_dir, wavs, tokens=None):
+    """--dump-outputs: what the timed path handed its caller in its last step, one row per utterance in a fixed order (global utterance /
+    stream index), as .npy files of at most ~50 MB together:
+      tokens.npy          float32 [n, max_len]  speech-token ids, -1 past the end of an utterance (not written without token ids)
+      wave_stats.npy      float64 [n, 4]        length, sum, sum of squares and max |x| of every whole waveform
+      wave_sample.npy     float32 [n, k]        each waveform at k positions drawn without replacement by a generator seeded with its length
+      wave_sample_pos.npy float64 [n, k]        those positions, ascending (-1 pads a waveform shorter than k); k = DUMP_WAVE_VALUES // n at most"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    w = [x.detach().reshape(-1).float().cpu().numpy() for x in wavs]
+    n = len(w)
+    k = min(max([len(x) for x in w] + [0]), DUMP_WAVE_VALUES // max(n, 1))
+    sample, pos = np.zeros((n, k), np.float32), np.full((n, k), -1.0, np.float64)
+    for i, x in enumerate(w):
+        p = np.arange(len(x)) if len(x) <= k else np.sort(np.random.default_rng(len(x)).choice(len(x), k, replace=False))
+        sample[i, :len(p)], pos[i, :len(p)] = x[p], p
+    stats = np.array([[len(x), x.sum(dtype=np.float64), np.square(x, dtype=np.float64).sum(), float(np.abs(x).max()) if len(x) else 0.0] for x in w],
+                     np.float64).reshape(n, 4)
+    np.save(os.path.join(out_dir, 'wave_stats.npy'), stats)
+    np.save(os.path.join(out_dir, 'wave_sample.npy'), sample)
+    np.save(os.path.join(out_dir, 'wave_sample_pos.npy'), pos)
+    if tokens is not None:
+        tok = np.full((n, max([len(t) for t in tokens] + [0])), -1.0, np.float32)
+        for i, t in enumerate(tokens):
+            tok[i, :len(t)] = np.asarray(list(t), np.float32)
+        np.save(os.path.join(out_dir, 'tokens.npy'), tok)
 
 
 def read_prof(lib):
@@ -380,6 +425,8 @@ def run_acoustic(args, cfg, world, rank, lib):
         t_flow, t_hift = t_flow + a, t_hift + b
     barrier()
     elapsed = time.time() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, [wavs[j] for j in sorted(range(n), key=lambda j: ids[j])])      # this rank's streams, by global index
     frames = float(sum(2 * m for m in lens)) * args.steps
     dit_flops = sum(7.56e9 * 2 * m + 1.80e6 * (2 * m) ** 2 for m in lens) * args.steps
     hift_flops = 672e6 * frames
@@ -520,21 +567,57 @@ def main():
             dist.barrier()
         sync()
 
+    last = {}                                        # what the most recent step returned to its caller (--dump-outputs)
+
     def step():
         wavs, st = pipe.synthesize(utts, max_token_text_ratio=ratio, min_token_text_ratio=ratio)
         got = gather_waveforms(wavs, gids, dst=0)
+        last.update(wavs=wavs, tokens=st.token_ids)
         return st, got
 
-    # Warm-up steps run the three stages back to back (this is also where the un-overlapped stage times come from).  The timed
-    # steps go through the software pipeline: the flow decoder + vocoder of step i run on a second stream while the LM decodes
-    # step i+1; the pipeline is empty when the clock starts and drained before it stops, so the region holds exactly K whole steps.
+    pace = [int(v) for v in args.lm_pace.split(',')] if args.lm_pace else None
+
+    def continuous_job(n_steps):
+        # K steps of B utterances each = K * B utterances through the continuous-batching engine; finished waveforms are handed to rank 0
+        # one step's worth (B utterances) at a time, inside the timed region
+        # the job is the GLOBAL list of steps x B x world utterances (global index = sampler seed), dealt longest-first across the ranks
+        # (dp.shard_by_cost, SURVEY.md §8(e)): with mixed lengths every rank gets the same amount of text, with equal lengths the deal is
+        # round-robin; no rank ever needs another's utterances, so this is still weak scaling with no data-path collective
+        n_global = n_steps * B * world
+        shards = shard_by_cost([float(n_text_of(g)) for g in range(n_global)], world)
+        mine = shards[rank]
+        assert len(mine) == n_steps * B or zero_shot
+        job = [make_utt(g) for g in mine]
+        hand = Handoff(shards, B, dst=0, keep=stub)
+        done = {}                                    # the last B utterances of this rank's job: its last step (--dump-outputs)
+        for i, wav, toks in pipe.synthesize_continuous(job, lm_slots=args.lm_slots, max_token_text_ratio=ratio, min_token_text_ratio=ratio,
+                                                       acoustic_batch=args.acoustic_batch, acoustic_min_batch=args.acoustic_min_batch, pace=pace):
+            hand.push(job[i].seed, wav)                # one step's worth (B utterances) per hand-off, inside the timed region
+            if args.dump_outputs and i >= len(job) - B:
+                done[i] = (wav, toks)
+        got = hand.finish()
+        assert rank != 0 or hand.n_received == n_global
+        if done:
+            order = sorted(done, key=lambda i: job[i].seed)
+            last.update(wavs=[done[i][0] for i in order], tokens=[done[i][1] for i in order])
+        return got, hand, shards
+
+    # Warm-up.  A plain run in continuous mode warms up on what it times: one job of W steps through the same engine (same grid, same
+    # acoustic stage).  Otherwise the W warm-up steps run the three stages back to back (this is also where the un-overlapped stage times
+    # come from), and --full follows them with the strict-batch step and the decode grid alone.  The timed steps of chains mode go through
+    # the software pipeline: the flow decoder + vocoder of step i run on a second stream while the LM decodes step i+1; the pipeline is
+    # empty when the clock starts and drained before it stops, so the region holds exactly K whole steps.
     serial = None
-    for _ in range(args.warmup):
-        serial, got = step()
+    if args.mode == 'continuous' and not args.full:
+        if args.warmup > 0:
+            continuous_job(args.warmup)
+    else:
+        for _ in range(args.warmup):
+            serial, got = step()
     # BASELINE configs[1] read strictly: ONE batch of B utterances, lock-step decode grid of B sequences, no utterance of another batch in
     # flight, stages back to back — its throughput and its latency (every utterance of the batch is complete after `latency_s`)
     strict = None
-    if args.warmup > 0:
+    if args.warmup > 0 and args.full:
         sync()
         t_s = time.time()
         serial, got = step()
@@ -544,13 +627,14 @@ def main():
                   'utterances_in_flight_per_gpu': B, 'schedule': 'one batch of %d, lock-step decode, stages back to back, no continuous batching (one un-timed extra step after the warm-up)' % B,
                   'stage_seconds': {'llm': round(serial.llm_seconds, 4), 'flow': round(serial.flow_seconds, 4), 'hift': round(serial.hift_seconds, 4)}}
     lm_alone = None
-    if args.mode == 'continuous' and args.warmup > 0 and not stub:
+    if args.mode == 'continuous' and args.warmup > 0 and not stub and args.full:
         # the wide decode grid alone (nothing else on the GPU): --lm-slots utterances through the engine, untimed — `roofline.alone`
         reqs = [dict(text=utts[i % B].text, seed=10_000 + i, tag=i, max_token_text_ratio=ratio, min_token_text_ratio=ratio) for i in range(args.lm_slots)]
         for _ in pipe.llm.generate_stream(iter(reqs), n_slots=args.lm_slots):
             pass
         lm_alone = dict(pipe.llm.last_stats)
     barrier()
+    last.clear()
     stats = []
     cont = None
     t0 = time.time()
@@ -563,33 +647,20 @@ def main():
                                                   lm_chains=args.lm_chains, acoustic_chains=args.acoustic_chains):
             got = gather_waveforms(wavs, gids, dst=0)
             stats.append(st)
+        last.update(wavs=wavs, tokens=st.token_ids)
     else:
-        # K steps of B utterances each = K * B utterances through the continuous-batching engine; finished waveforms are handed to rank 0
-        # one step's worth (B utterances) at a time, inside the timed region
-        # the job is the GLOBAL list of steps x B x world utterances (global index = sampler seed), dealt longest-first across the ranks
-        # (dp.shard_by_cost, SURVEY.md §8(e)): with mixed lengths every rank gets the same amount of text, with equal lengths the deal is
-        # round-robin; no rank ever needs another's utterances, so this is still weak scaling with no data-path collective
-        n_global = args.steps * B * world
-        shards = shard_by_cost([float(n_text_of(g)) for g in range(n_global)], world)
-        mine = shards[rank]
-        assert len(mine) == args.steps * B or zero_shot
-        job = [make_utt(g) for g in mine]
-        hand = Handoff(shards, B, dst=0, keep=stub)
-        for i, wav, toks in pipe.synthesize_continuous(job, lm_slots=args.lm_slots, max_token_text_ratio=ratio, min_token_text_ratio=ratio,
-                                                       acoustic_batch=args.acoustic_batch, acoustic_min_batch=args.acoustic_min_batch,
-                                                       pace=[int(v) for v in args.lm_pace.split(',')] if args.lm_pace else None):
-            hand.push(job[i].seed, wav)                # one step's worth (B utterances) per hand-off, inside the timed region
-        got = hand.finish()
-        assert rank != 0 or hand.n_received == n_global
+        got, hand, shards = continuous_job(args.steps)
         cont = dict(pipe.last_continuous)
     barrier()
     elapsed = time.time() - t0
-    # Per-kernel durations: hipEvent brackets on the launch stream, every `prof_period`-th launch of each kernel class.
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last['wavs'], last['tokens'])          # rank 0's utterances of the last timed step, by global index
+    # Per-kernel durations (--full): hipEvent brackets on the launch stream, every `prof_period`-th launch of each kernel class.
     # A hipGraph replay cannot be bracketed per kernel, so the brackets run over one more, identical step with the decode
     # graph disabled (same kernels, same launch geometry; the rocprofv3 --kernel-trace summary under profiles/ covers the
     # graph-replayed timed steps themselves and must agree).
     prof = {}
-    if rank == 0 and not stub:
+    if rank == 0 and not stub and args.full:
         lib.hvx_prof_enable(args.prof_period)
         step_prof_t0 = time.time()
         pipe.synthesize(utts, max_token_text_ratio=ratio, min_token_text_ratio=ratio)
@@ -836,7 +907,7 @@ def main():
             torch.cuda.empty_cache()
         except Exception as e:
             line['exact_vocoder'] = {'value': None, 'error': repr(e)}
-    if world == 1 and not args.tiny and args.config == 'tts' and args.mode == 'continuous' and args.llm_dtype == 'bf16':
+    if world == 1 and args.full and not args.tiny and args.config == 'tts' and args.mode == 'continuous' and args.llm_dtype == 'bf16':
         # north_star's parity clause (ids bit-exact; mel / waveform 1e-3) against what each measured mode delivers, in ONE place.  The distances are what
         # the GPU tests assert against the REFERENCE's own outputs at these shapes (tests/test_gpu_refpin.py, test_gpu_cv3d.py), not measured in this run.
         def _v(k):
@@ -859,8 +930,8 @@ def main():
         line['configs'] = {}
         for name, extra in (('stress', []), ('zero_shot', []), ('acoustic', [])):
             try:
-                cmd = [sys.executable, os.path.abspath(__file__), '--config', name, '--steps', str(args.config_steps), '--warmup', '1', '--no-cpu-baseline', '--no-fp32-mode',
-                       '--no-extras', '--config-steps', '0'] + extra
+                cmd = [sys.executable, os.path.abspath(__file__), '--config', name, '--steps', str(args.config_steps), '--warmup', '1', '--full', '--no-cpu-baseline',
+                       '--no-fp32-mode', '--no-extras', '--config-steps', '0'] + extra
                 t_c = time.time()
                 out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420)
                 js = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]

@@ -716,22 +716,18 @@ def test_hydravox_yaml_dimensions(tmp_path):
     assert config_from_model_dir(str(tmp_path)) is None
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='reference tree not present (GPU box)')
 def test_yaml_fixture_uses_only_real_constructor_arguments():
-    """every key the test yaml gives a `!new:` node is an argument of that reference class's __init__ (checked on the sources' AST:
-    the modules themselves need packages that are absent here)"""
-    import ast
+    """every key the test yaml gives a `!new:` node is an argument of that reference class's __init__ (the argument names were read from the
+    reference sources' AST into tests/golden/ctor_args.json by tests/golden/make_golden_ctor_args.py: the modules themselves need packages that are absent here)"""
+    import json
     from flowmirror_hydravox_amd.yaml_config import load_hyperpyyaml_plain
-    base = '/root/reference/server/model_utils/'
+    with open(os.path.join(ROOT, 'tests', 'golden', 'ctor_args.json')) as f:
+        ctor_args = json.load(f)
     doc = load_hyperpyyaml_plain(_YAML)
 
     def init_args(tag):
-        mod, cls = tag.split(':', 1)[1].rsplit('.', 1)
-        path = base + mod.replace('.', '/') + '.py'
-        tree = ast.parse(open(path, encoding='utf-8').read())
-        c = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == cls)
-        f = next(n for n in c.body if isinstance(n, ast.FunctionDef) and n.name == '__init__')
-        return {a.arg for a in f.args.args + f.args.kwonlyargs} - {'self'}
+        assert tag in ctor_args, ('class not in tests/golden/ctor_args.json: re-mint it', tag)
+        return set(ctor_args[tag])
 
     def walk(node, seen):
         if isinstance(node, dict):

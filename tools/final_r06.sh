@@ -9,8 +9,8 @@ T0=$(date +%s)
 timeout 2400 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; grep -E "passed|failed" $O/pytest_gpu.log | tail -1
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 echo "tests wall $(( $(date +%s) - T0 )) s"
-T0=$(date +%s); timeout 1700 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.log 2> $O/bench.err; echo "bench wall $(( $(date +%s) - T0 )) s"; tail -1 $O/bench.log | cut -c1-200
-B="python bench.py --steps 8 --no-cpu-baseline --no-fp32-mode --no-extras"
+T0=$(date +%s); timeout 1700 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.log 2> $O/bench.err; echo "bench wall $(( $(date +%s) - T0 )) s"; tail -1 $O/bench.log | cut -c1-200
+B="python bench.py --steps 8 --full --no-cpu-baseline --no-fp32-mode --no-extras"
 timeout 900 $B --config stress > $O/stress.log 2>&1
 timeout 500 $B --config zero_shot > $O/zero_shot.log 2>&1
 timeout 500 $B --config acoustic > $O/acoustic.log 2>&1
