@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HVX_LIB_PATH') or os.path.join(HERE, 'libhvx.so')
 LIB_EXPLICIT = bool(os.environ.get('HVX_LIB_PATH'))
 
-F32, BF16 = 0, 1
+F32, BF16, F16 = 0, 1, 2
 
 # Act codes (csrc/hvx_device.h)
 ACT_NONE, ACT_GELU_TANH, ACT_SILU, ACT_MISH, ACT_ELU, ACT_LRELU, ACT_SNAKE, ACT_TANH, ACT_ABS = range(9)
@@ -310,7 +310,9 @@ def dtype_code(torch_dtype):
         return F32
     if torch_dtype == torch.bfloat16:
         return BF16
-    raise HvxError('unsupported dtype %s (hvx computes in bf16 or f32)' % torch_dtype)
+    if torch_dtype == torch.float16:
+        return F16                   # (the flow's fp16 mode, HvxFlow(dtype=torch.float16), and the fp16 DiT kernels it runs)
+    raise HvxError('unsupported dtype %s (hvx computes in bf16, f32, or f16 in the flow)' % torch_dtype)
 
 
 def ptr_array(tensors):

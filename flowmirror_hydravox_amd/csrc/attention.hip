@@ -397,10 +397,12 @@ __global__ void attn_combine_kernel(AttnArgs a) {
 // are re-filled in place one MFMA pair behind their last use (K(t + 1) during QK(3, t), V(t) during PV(3, t - 1)), so the working set is the in-tile form's — minus the 16
 // registers of the per-row reference, which this form drops (scores start from 0; see the step's comment and the vote after the loop): with them the loop spills.
 // Measured at B = 8, H = 16, T = 5632: 849 against 967 us (profiles/r06_attn_tile_ab.md), flow solve 398.7 against 419.6 ms.
-template <int QR, bool FAST, bool PRE, int LAB = 0, int NW = 4, int ROT = 0>   // 16-row query tiles per wave: every K / V^T fragment read from LDS feeds QR MFMAs
+template <int QR, bool FAST, bool PRE, int LAB = 0, int NW = 4, int ROT = 0, class T = bf16_t>   // 16-row query tiles per wave: every K / V^T fragment read from LDS feeds QR MFMAs
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(AttnArgs a) {
     static_assert(ROT == 0 || (QR == 4 && FAST && PRE && LAB == 0 && NW == 4), "the rotated pipeline exists for the 64-row, pre-scaled fast form");
-    typedef bf16_t T;
+    static_assert(!FAST || std::is_same<T, bf16_t>::value, "the fixed-reference and reference-free tiles rely on bf16's exponent range: fp16 takes the classical loop");
+    typedef typename Vec8<T>::type T8;
+    typedef typename Vec4<T>::type T4;
     constexpr int KT = 64;                 // keys per tile
     constexpr int LD = 72;                 // LDS row stride (elements): 144 B keeps the 16 rows of a lane group on distinct 16-B slots
     __shared__ __attribute__((aligned(16))) T Ks[2][KT * LD];
@@ -439,7 +441,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
 #pragma unroll
     for (int i = 0; i < QR; ++i) lim[i] = a.chunk > 0 ? min(kv_len, ((row0 + i * 16 + fr) / a.chunk + 1) * a.chunk) : kv_len;
 
-    bf16x8 qf[QR][2];
+    T8 qf[QR][2];
 #pragma unroll
     for (int i = 0; i < QR; ++i) {
         const int r = row0 + i * 16 + fr;
@@ -454,7 +456,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
     }
     // tile loader: thread t moves NLD x 16 B of K (rows t/8 [and t/8+32], chunk t%8) and NLD x 16 B of V^T
     const int lrow = tid >> 3, lchunk = (tid & 7) * 8;
-    bf16x8 rk[NLD], rv[NLD];
+    T8 rk[NLD], rv[NLD];
     auto gload = [&](int key0) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
@@ -473,14 +475,14 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             store8(&Ks[buf][(lrow + i * 32) * LD + lchunk], rk[i]);
-            bf16x4 lo, hi;
+            T4 lo, hi;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 lo[j] = rv[i][j];
                 hi[j] = rv[i][4 + j];
             }
-            *reinterpret_cast<bf16x4*>(&Vs[buf][(lrow + i * 32) * LD + vpos]) = lo;
-            *reinterpret_cast<bf16x4*>(&Vs[buf][(lrow + i * 32) * LD + vpos + 8]) = hi;
+            *reinterpret_cast<T4*>(&Vs[buf][(lrow + i * 32) * LD + vpos]) = lo;
+            *reinterpret_cast<T4*>(&Vs[buf][(lrow + i * 32) * LD + vpos + 8]) = hi;
         }
     };
 
@@ -496,9 +498,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
     }
     const float c = PRE ? 1.0f : a.scale * 1.4426950408889634f;         // softmax(s * scale) == exp2(s * c - m * c); PRE: c sits in q
     const f32x2 c2 = {c, c};
-    bf16x8 ones;
+    // probabilities and outputs go to T by round-to-nearest: in the classical loop p <= 1, and an output row is a convex combination of V^T values, so neither
+    // can leave fp16's range (the saturation of the QKV epilogue, +-65504, bounds q / k / V^T on the way in)
+    auto cvt = [](float v) __attribute__((always_inline)) { return (T)v; };
+    T8 ones;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) ones[e] = f32_to_bf16(1.0f);
+    for (int e = 0; e < 8; ++e) ones[e] = cvt(1.0f);
 
     // One 64-key tile.  The softmax is the bottleneck of this kernel, not the matrix cores (head_dim 64: 32 MFMAs against ~32
     // exp2 + ~100 other VALU instructions per wave and tile), so everything that can leave the vector ALU does: the row sums are
@@ -510,8 +515,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
         f32x4 s[QR][4];
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
-            const bf16x8 k0 = load8(&Ks[buf][(kt * 16 + fr) * LD + fg * 8]);
-            const bf16x8 k1 = load8(&Ks[buf][(kt * 16 + fr) * LD + 32 + fg * 8]);
+            const T8 k0 = load8(&Ks[buf][(kt * 16 + fr) * LD + fg * 8]);
+            const T8 k1 = load8(&Ks[buf][(kt * 16 + fr) * LD + 32 + fg * 8]);
 #pragma unroll
             for (int i = 0; i < QR; ++i) {
                 s[i][kt] = f32x4{0, 0, 0, 0};
@@ -519,7 +524,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
                 mma32(s[i][kt], k1, qf[i][1]);
             }
         }
-        bf16x8 pf[QR][2];
+        T8 pf[QR][2];
 #pragma unroll
         for (int i = 0; i < QR; ++i) {
             if constexpr (TAIL) {
@@ -550,7 +555,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
                     p[4 * hh + 3] = __builtin_amdgcn_exp2f(hi[1]);
                 }
 #pragma unroll
-                for (int e = 0; e < 8; ++e) pf[i][m][e] = f32_to_bf16(p[e]);
+                for (int e = 0; e < 8; ++e) pf[i][m][e] = cvt(p[e]);
             }
             if (__any(m_new != m_run[i])) {                              // wave-uniform: most tiles do not raise any row's maximum
                 const float alpha = __builtin_amdgcn_exp2f(m_run[i] - m_new);     // exp2(-inf) == 0 on the first tile
@@ -572,7 +577,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
         for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
-                const bf16x8 v = load8(&Vs[buf][(dt * 16 + fr) * LD + m * 32 + fg * 8]);
+                const T8 v = load8(&Vs[buf][(dt * 16 + fr) * LD + m * 32 + fg * 8]);
 #pragma unroll
                 for (int i = 0; i < QR; ++i) mma32(o_acc[i][dt], v, pf[i][m]);
             }
@@ -588,6 +593,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
                 if (key0 + kt * 16 + fg * 4 + r >= lim[i]) sv[kt][r] = -INFINITY;
     };
     auto tile_fast = [&](int buf, int key0, auto tail_tag) {
+        if constexpr (FAST) {                                          // (bf16 only: not instantiated for the classical fp16 tile)
         constexpr bool TAIL = decltype(tail_tag)::value;
         bf16x8 kf[4][2], vf[4][2];
 #pragma unroll
@@ -709,6 +715,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
             sm(1, sb, pb); pv(0, pa);
             pin(std::integral_constant<int, 10>{}, std::integral_constant<int, PRE ? 3 : 4>{});
             pv(1, pb);
+        }
         }
     };
 
@@ -925,10 +932,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
         T* op = reinterpret_cast<T*>(a.out) + (long long)b * a.o_bs + (long long)h * a.o_hs + (long long)r * a.o_lo;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-            bf16x4 o4;
+            T4 o4;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o4[e] = f32_to_bf16(o_acc[i][dt][e] * inv);
-            *reinterpret_cast<bf16x4*>(op + dt * 16 + fg * 4) = o4;
+            for (int e = 0; e < 4; ++e) o4[e] = cvt(o_acc[i][dt][e] * inv);
+            *reinterpret_cast<T4*>(op + dt * 16 + fg * 4) = o4;
         }
     }
 }
@@ -1757,6 +1764,28 @@ static int launch_t(const AttnArgs& a_in, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : (set_error("attention launch failed"), -1);
 }
 
+// IEEE fp16 operands (the flow's DT_F16 mode): the DiT tile only, always in its classical form — running row maximum, p = exp2(s - m) <= 1 stored as fp16 for the
+// value and row-sum MFMAs (v_mfma_f32_16x16x32_f16), fp32 row sums, fp16 output.  The bf16 forms' fixed-reference (form 16) and reference-free (rotated, form 0)
+// probabilities may exceed 1 by up to bf16's exponent range, which fp16 (max 65504) does not have; attn_dit_form selects among the bf16 forms only.
+static int launch_dit_f16(const AttnArgs& a, hipStream_t s) {
+    if (a.causal || a.n_splits != 1 || a.kn < a.n_rows || a.kv_slot || a.n_valid_lo || a.kv_frag || a.o_frag_kt > 0 || (a.v_ld & 63))
+        return set_error("launch_attention: fp16 operands exist for the DiT tile only (non-causal, one split, no cache slots, v_ld %% 64 == 0)"), -1;
+    const double fl = 4.0 * a.n_rows * (double)a.kv_len_const * 64.0 * a.heads * a.batch;
+    const int slot = prof_begin(PK_ATTN, a.kv_len ? 0.0 : fl, s);
+    // 64 query rows per wave on long unmasked sequences, 32 otherwise (the bf16 tile's choice, same reasons)
+    if (a.n_rows >= 2048 && a.chunk <= 0) {
+        const dim3 g4((a.n_rows + 255) / 256, a.heads, a.batch);
+        if (a.q_log2) hipLaunchKernelGGL((attn_dit_kernel<4, false, true, 0, 4, 0, f16_t>), g4, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((attn_dit_kernel<4, false, false, 0, 4, 0, f16_t>), g4, dim3(256), 0, s, a);
+    } else {
+        const dim3 g2((a.n_rows + 127) / 128, a.heads, a.batch);
+        if (a.q_log2) hipLaunchKernelGGL((attn_dit_kernel<2, false, true, 0, 4, 0, f16_t>), g2, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((attn_dit_kernel<2, false, false, 0, 4, 0, f16_t>), g2, dim3(256), 0, s, a);
+    }
+    prof_end(slot, s);
+    return hipGetLastError() == hipSuccess ? 0 : (set_error("attention launch failed"), -1);
+}
+
 int launch_attention(const AttnArgs& a_in, hipStream_t s) {
     AttnArgs a = a_in;
     if (a.n_rows <= 0 || a.batch <= 0) return 0;
@@ -1771,6 +1800,7 @@ int launch_attention(const AttnArgs& a_in, hipStream_t s) {
         set_error("launch_attention: bad geometry v_ld=%d split_chunk=%d", a.v_ld, a.split_chunk);
         return -1;
     }
+    if (a.dtype == DT_F16) return launch_dit_f16(a, s);
     return a.dtype == DT_BF16 ? launch_t<bf16_t>(a, s) : launch_t<float>(a, s);
 }
 

@@ -9,15 +9,18 @@
 //
 // LDS images are [k-half][row][32 bf16] (64-byte rows, lane-linear as the DMA deposits them); the lane that fills 16-byte slot s of row r fetches chunk
 // s ^ f(r), f(r) = (-(r >> 2)) & 3 (r within its 16-row group), which puts the 16 lanes of every ds_read_b128 lane group on 16 distinct slots.
+//
+// T: bf16, or IEEE fp16 (v_mfma_f32_16x16x32_f16) in the flow's fp16 mode, where this form takes the position-embedding convolutions at every length (the tiled
+// forms have no fp16 instantiation); the Mish output of the first convolution is then written as fp16 (round to nearest, saturated at +-65504).
 #include "gemm_epilogue.h"
 
 namespace hvx {
 
 namespace {
 
-template <int MAXR, int TPS>
+template <int MAXR, int TPS, class T = bf16_t>
 __global__ __launch_bounds__(256) void gconv64_kernel(GemmArgs a) {
-    typedef bf16_t T;
+    typedef typename Vec8<T>::type T8;
     constexpr int BM = 128, MT = 2, NT = 4, WN = 64;
     constexpr int SLD = WN + 4, ROWS_PASS = 16;
     constexpr int AIMG = MAXR * 32;                        // one k-half image of the input rows: [MAXR][32]
@@ -83,7 +86,7 @@ __global__ __launch_bounds__(256) void gconv64_kernel(GemmArgs a) {
             const T* const bt = Bs + (((st & 1) * TPS + ts) * 2) * BIMG;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                bf16x8 af[MT], bf[NT];
+                T8 af[MT], bf[NT];
 #pragma unroll
                 for (int i = 0; i < MT; ++i) af[i] = load8(As + h * AIMG + (j0 + i * 16) * 32 + asw);
 #pragma unroll
@@ -104,13 +107,20 @@ __global__ __launch_bounds__(256) void gconv64_kernel(GemmArgs a) {
 // 1 = launched, 0 = not eligible (the caller falls through to the tiled forms), -1 = error
 int launch_conv_resident(const GemmArgs& a, hipStream_t s) {
     constexpr int MAXR = 160;
-    if (a.dtype != DT_BF16 || a.epi != EPI_GENERIC || a.cin_pad != 64 || a.N > 64 || a.conv_stride != 1 || a.up != 1 || a.K < 128 || a.M < 2048 ||
-        (a.lda & 7) || (a.a_gs & 7) || (a.a_bs & 7) || 128 + (a.K / 64 - 1) * a.conv_dil > MAXR || a.a_planes || a.w_planes)
+    const bool f16 = a.dtype == DT_F16;
+    const bool shape_ok = a.epi == EPI_GENERIC && a.cin_pad == 64 && a.N <= 64 && a.conv_stride == 1 && a.up == 1 && a.K >= 128 && !(a.lda & 7) && !(a.a_gs & 7) &&
+                          !(a.a_bs & 7) && 128 + (a.K / 64 - 1) * a.conv_dil <= MAXR && !a.a_planes && !a.w_planes && (long long)a.batch * a.groups <= 65535;
+    if (f16 && a.cin_pad == a.K) return 0;                // (an fp16 Linear: gemm_big.hip)
+    if (f16) {
+        // fp16 convolutions exist in this form only: every length takes it (rows past M are neither read nor stored)
+        if (!shape_ok) return set_error("conv: fp16 operands are supported for 64-channel-per-group convolutions with 2..%d taps only", (MAXR - 128) / (a.conv_dil > 0 ? a.conv_dil : 1) + 1), -1;
+    } else if (a.dtype != DT_BF16 || !shape_ok || a.M < 2048) {
         return 0;
+    }
     const long long gz = (long long)a.batch * a.groups;
-    if (gz > 65535) return 0;
     const int slot = prof_begin(PK_GEMM, 2.0 * a.M * a.N * (double)a.K * a.batch * a.groups, s);
-    hipLaunchKernelGGL((gconv64_kernel<MAXR, 2>), dim3((a.M + 127) / 128, 1, (unsigned)gz), dim3(256), 0, s, a);
+    if (f16) hipLaunchKernelGGL((gconv64_kernel<MAXR, 2, f16_t>), dim3((a.M + 127) / 128, 1, (unsigned)gz), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gconv64_kernel<MAXR, 2>), dim3((a.M + 127) / 128, 1, (unsigned)gz), dim3(256), 0, s, a);
     prof_end(slot, s);
     return hipGetLastError() == hipSuccess ? 1 : (set_error("conv (resident-row form) launch failed"), -1);
 }

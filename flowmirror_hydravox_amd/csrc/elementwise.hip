@@ -604,6 +604,7 @@ __global__ void rows_to_dtype_kernel(const float* src, int ld_src, D* dst, int l
 int launch_rows_to_dtype(const float* src, int ld_src, void* dst, int dd, int ld_dst, int rows, int cols, int cols_pad, hipStream_t s) {
     if (rows <= 0) return 0;
     if (dd == DT_BF16) hipLaunchKernelGGL(rows_to_dtype_kernel<bf16_t>, dim3(rows), dim3(128), 0, s, src, ld_src, (bf16_t*)dst, ld_dst, cols, cols_pad);
+    else if (dd == DT_F16) hipLaunchKernelGGL(rows_to_dtype_kernel<f16_t>, dim3(rows), dim3(128), 0, s, src, ld_src, (f16_t*)dst, ld_dst, cols, cols_pad);   // (saturated at +-65504)
     else hipLaunchKernelGGL(rows_to_dtype_kernel<float>, dim3(rows), dim3(128), 0, s, src, ld_src, (float*)dst, ld_dst, cols, cols_pad);
     return hipGetLastError() == hipSuccess ? 0 : (set_error("rows_to_dtype launch failed"), -1);
 }

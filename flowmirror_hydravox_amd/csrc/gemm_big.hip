@@ -26,8 +26,9 @@ constexpr int BM = 256, WM = 128, WN = 64, MT = WM / 16, NT = WN / 16;
 // <BN 256, BK 64, 8 waves>: one workgroup per CU (128 KiB of LDS), 2 x 4 waves.  (A <BN 128, BK 32, 4 waves> form — TWO independent
 // workgroups per CU, 48 KiB each, so that one's epilogue runs under the other's K-loop — was correct but 3-10 % slower on every DiT Linear,
 // with or without a deliberate half-tile start offset between the two co-resident workgroups: 1.5x the L2 -> LDS bytes per flop)
-// T: the operand type — bf16, or IEEE fp16 for the DiT block Linears of a handle that runs them in the reference's deployed dtype (DT_F16); the QKV
-// epilogue writes q / k / V^T for the attention in bf16 either way
+// T: the operand type — bf16, or IEEE fp16 for the DiT block Linears of a handle that runs them in the reference's deployed dtype (DT_F16)
+// QT: the type the QKV epilogue writes q / k / V^T in — bf16 (the bf16 mode's attention, whatever T is), or fp16 for the fp16 flow mode's attention
+// (GemmArgs.qkv_f16)
 // MS: the MFMA shape of the K-loop — 16 (v_mfma_f32_16x16x32: 64 instructions of 16 cycles per K-tile and wave) or 32 (v_mfma_f32_32x32x16: 32 instructions of
 // 32 cycles, the shape the matrix pipe sustains 12-15 % faster and that leaves twice the issue slots per matrix cycle for the fragment reads and the DMA; the
 // accumulators are then 4 x 2 tiles of 32 x 32, the same 128 registers, and the epilogue stages them through acc_stage's second form).  Same sums per output
@@ -35,7 +36,7 @@ constexpr int BM = 256, WM = 128, WN = 64, MT = WM / 16, NT = WN / 16;
 __device__ __forceinline__ f32x16_epi mfma32(const bf16x8& x, const bf16x8& y, const f32x16_epi& c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16_epi mfma32(const f16x8& x, const f16x8& y, const f32x16_epi& c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, c, 0, 0, 0); }
 
-template <int EPI, int BN, int BK, int NWAVE, class T, int MS = 16>
+template <int EPI, int BN, int BK, int NWAVE, class T, int MS = 16, class QT = bf16_t>
 __global__ __launch_bounds__(NWAVE * 64, 2) void gemm_big_kernel(GemmArgs a, int tiles_m, int tiles_n, int gw) {
     constexpr int TILE_ELEMS = (BM + BN) * BK;               // one K-tile of A and W (bf16 elements)
     constexpr int WAVES_N = BN / WN;
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void gemm_big_kernel(GemmArgs a, int
         if (nk >= 2) iter(nk - 2, std::false_type{}, std::true_type{});
         iter(nk - 1, std::false_type{}, std::false_type{});
         __syncthreads();                                 // the epilogue reuses the tile memory as staging
-        gemm_epilogue<T, MT, NT, WN, EPI, 1, bf16_t>(a, acc, reinterpret_cast<float*>(smem) + wave * SCR_FLOATS, lane, m0 + wm0, n0 + wn0, bz, 0);
+        gemm_epilogue<T, MT, NT, WN, EPI, 1, QT>(a, acc, reinterpret_cast<float*>(smem) + wave * SCR_FLOATS, lane, m0 + wm0, n0 + wn0, bz, 0);
         return;
     }
     f32x4 acc[MT][NT];
@@ -235,11 +236,11 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void gemm_big_kernel(GemmArgs a, int
     {   // (lab: the whole epilogue's instructions, but only row 0 is stored and every residual row read is row 0: no memory traffic to speak of)
         GemmArgs a2 = a;
         a2.M = 1;
-        gemm_epilogue<T, MT, NT, WN, EPI, 1, bf16_t>(a2, acc, reinterpret_cast<float*>(smem) + wave * SCR_FLOATS, lane, m0 + wm0, n0 + wn0, bz, 0);
+        gemm_epilogue<T, MT, NT, WN, EPI, 1, QT>(a2, acc, reinterpret_cast<float*>(smem) + wave * SCR_FLOATS, lane, m0 + wm0, n0 + wn0, bz, 0);
         return;
     }
 #endif
-    gemm_epilogue<T, MT, NT, WN, EPI, 1, bf16_t>(a, acc, reinterpret_cast<float*>(smem) + wave * SCR_FLOATS, lane, m0 + wm0, n0 + wn0, bz, 0);
+    gemm_epilogue<T, MT, NT, WN, EPI, 1, QT>(a, acc, reinterpret_cast<float*>(smem) + wave * SCR_FLOATS, lane, m0 + wm0, n0 + wn0, bz, 0);
 }
 
 template <int BN, int BK, int NWAVE>
@@ -269,6 +270,7 @@ int launch_form(const GemmArgs& a, hipStream_t s, long long min_tiles) {
 #endif
     if (a.dtype == DT_F16) {
         if (a.epi == EPI_GENERIC) HVX_BIG(EPI_GENERIC, f16_t);
+        else if (a.qkv_f16) hipLaunchKernelGGL((gemm_big_kernel<EPI_QKV_DIT, BN, BK, NWAVE, f16_t, 16, f16_t>), grid, block, 0, s, a, tiles_m, tiles_n, gw);
         else HVX_BIG(EPI_QKV_DIT, f16_t);
     } else {
         if (a.epi == EPI_GENERIC) HVX_BIG(EPI_GENERIC, bf16_t);

@@ -268,11 +268,12 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
     }
     const int x3 = launch_gemm_x3(a, s);                   // fp32 operands split into bf16 pairs (gemm_x3.hip), where the caller allows it
     if (x3) return x3 < 0 ? -1 : 0;
-    const int resident = (int)opt(OPT_CONV_RESIDENT);      // (A/B option conv_resident)
-    const int rc = resident ? launch_conv_resident(a, s) : 0;   // 64-channel-per-group bf16 convolutions with their input rows resident in LDS
+    const int resident = (int)opt(OPT_CONV_RESIDENT) || a.dtype == DT_F16;      // (A/B option conv_resident; fp16 convolutions exist in the resident form only)
+    const int rc = resident ? launch_conv_resident(a, s) : 0;   // 64-channel-per-group convolutions with their input rows resident in LDS
     if (rc) return rc < 0 ? -1 : 0;
     const int big = launch_gemm_big(a, s);                 // the 256 x 256 tile form takes the large bf16 Linears (gemm_big.hip)
     if (big) return big < 0 ? -1 : 0;
+    if (a.dtype == DT_F16) return set_error("launch_gemm: no tile form takes fp16 operands for M=%d N=%d K=%d groups=%d", a.M, a.N, a.K, a.groups), -1;
     return a.dtype == DT_BF16 ? launch_t<bf16_t>(a, s) : launch_t<float>(a, s);
 }
 

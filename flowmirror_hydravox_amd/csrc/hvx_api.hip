@@ -264,6 +264,7 @@ int hvx_op_resample_linear(const float* x, int32_t rows, int32_t t_in, float* y,
 
 int hvx_op_skinny_gemm(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* Wpacked, const float* bias,
                        int32_t split_k, float* part_ws, float* out_f32, int32_t ldo, hvx_stream s) {
+    if (dtype != DT_F32 && dtype != DT_BF16) return set_error("hvx_op_skinny_gemm: dtype %d: fp32 (0) or bf16 (1) only", dtype), -1;
     SkinnyArgs k;
     memset(&k, 0, sizeof(k));
     k.dtype = dtype; k.M = M; k.N = N; k.K = K; k.A = A; k.lda = lda; k.W = Wpacked; k.nz = 1;

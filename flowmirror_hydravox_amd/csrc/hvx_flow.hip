@@ -10,7 +10,9 @@
 // Data layout in HBM: activations are time-major rows [B][T][C] (C contiguous) so that every Linear and every
 // Conv1d is one implicit-GEMM launch; GEMM operands are `dtype`; the DiT's residual stream is fp32 in fp32 mode and IEEE fp16 in bf16 mode
 // (hvx_flow_set_half_stream; the reference runs the whole decoder in fp16, infer_speech_model.py:103 — the updates are still formed in fp32
-// and rounded once per residual add); q/k are written
+// and rounded once per residual add).  fp16 mode (DT_F16): every matrix-core operand of the DiT — block Linears incl. the attention's out-projection,
+// q / k / V^T and the probabilities, the position-embedding convolutions — is IEEE fp16; the residual stream, the small Linears (time MLP, adaLN
+// modulation, input / output projection), the token encoder and the solver state are fp32 (tools/flow_fp16_study.py); q/k are written
 // head-major and V already transposed by the QKV epilogue, which is what the attention kernel consumes.
 #include <string.h>
 
@@ -111,8 +113,11 @@ size_t carve_est(const hvx_flow_config& c, char* base, int B, int T, EstBufs& b)
     return cv.off;
 }
 
+// operand type of the token encoder's pre-lookahead convolutions: fp32 in the fp16 mode (as in the fp32 mode)
+int enc_dtype(const hvx_flow_config& c) { return c.dtype == DT_F16 ? (int)DT_F32 : c.dtype; }
+
 size_t carve_enc(const hvx_flow_config& c, char* base, int n, EstBufs& b) {
-    const size_t es = dtype_size(c.dtype);
+    const size_t es = dtype_size(enc_dtype(c));
     const int melp = (c.mel + 31) & ~31;
     Carve cv(base);
     b.e_h0 = cv.take<float>((size_t)n * c.mel * 4);
@@ -179,15 +184,16 @@ int prelookahead(const hvx_flow* h, hipStream_t s, EstBufs& b, const float* x, i
     const hvx_flow_config& c = h->c;
     const int melp = (c.mel + 31) & ~31;
     const void* const* w = h->w.data();
-    HVX_CHECK(launch_rows_to_dtype(x, c.mel, b.e_h0t, c.dtype, melp, n, c.mel, melp, s));
+    const int edt = enc_dtype(c);
+    HVX_CHECK(launch_rows_to_dtype(x, c.mel, b.e_h0t, edt, melp, n, c.mel, melp, s));
     // conv1: Conv1d(mel -> C, k = len+1), input right-padded by `len` zeros, LeakyReLU(0.01)
-    GemmArgs g = linear(c.dtype, n_out, c.pla_channels, (c.pla_len + 1) * melp, b.e_h0t, melp, w[5], (const float*)w[6]);
+    GemmArgs g = linear(edt, n_out, c.pla_channels, (c.pla_len + 1) * melp, b.e_h0t, melp, w[5], (const float*)w[6]);
     g.cin_pad = melp; g.rows_in = n;
     g.act = ACT_LRELU; g.act_param = 0.01f;
     g.out = b.e_c1; g.out_f32 = 0; g.ldo = c.pla_channels; g.out_cols = c.pla_channels;
     HVX_CHECK(launch_gemm(g, s));
     // conv2: left pad 2, Conv1d(C -> mel, k = 3), + residual
-    g = linear(c.dtype, n_out, c.mel, 3 * c.pla_channels, b.e_c1, c.pla_channels, w[7], (const float*)w[8]);
+    g = linear(edt, n_out, c.mel, 3 * c.pla_channels, b.e_c1, c.pla_channels, w[7], (const float*)w[8]);
     g.cin_pad = c.pla_channels; g.rows_in = n_out; g.pad_left = 2;
     g.res = x; g.ldres = c.mel;
     g.out = y; g.out_f32 = 1; g.ldo = c.mel; g.out_cols = c.mel;
@@ -211,8 +217,8 @@ int estimator_core(const hvx_flow* h, hipStream_t s, EstBufs& b, int B, int T, c
     GemmArgs g;
     const void* const* tw = w + 19 + 10 * c.depth;
     // operand type of the SMALL Linears (time MLP, adaLN modulation, input / output projection): exact fp32 when the handle was told so — with fp16 block
-    // Linears these carry the bf16 mode's remaining distance from fp32 (tools/dit_rounding_study.py); a few ms per solve
-    const int sdt = (h->f32_small && dt == DT_BF16) ? DT_F32 : dt;
+    // Linears these carry the bf16 mode's remaining distance from fp32 (tools/dit_rounding_study.py); a few ms per solve.  Always fp32 in the fp16 mode.
+    const int sdt = ((h->f32_small && dt == DT_BF16) || dt == DT_F16) ? DT_F32 : dt;
     if (!skip_mods) {
     HVX_CHECK(launch_time_sinus(t, b.tsin, sdt, MB, c.time_freq_dim, s));
     g = linear(sdt, MB, D, c.time_freq_dim, b.tsin, c.time_freq_dim, w[9], (const float*)w[10]);
@@ -279,6 +285,7 @@ int estimator_core(const hvx_flow* h, hipStream_t s, EstBufs& b, int B, int T, c
         g.batch = B; g.a_bs = (long long)T * D; g.epi = EPI_QKV_DIT;
         g.q = b.q; g.k = b.k; g.vT = b.vT; g.heads = H; g.t_pad = Tp; g.rope_cos = (const float*)w[0]; g.rope_sin = (const float*)w[1];
         g.q_scale = 0.125f * 1.4426950408889634f;              // dim_head^-0.5 (modules.py:391, SDPA default scale) in log2 units, rounded once with q
+        g.qkv_f16 = dt == DT_F16;                              // (q / k / V^T in the attention's operand type: bf16 unless the whole DiT runs in fp16)
         HVX_CHECK(launch_gemm(g, s));
         AttnArgs at;
         memset(&at, 0, sizeof(at));
@@ -289,7 +296,7 @@ int estimator_core(const hvx_flow* h, hipStream_t s, EstBufs& b, int B, int T, c
         at.kv_len = kv_len; at.kv_len_const = T; at.causal = 0; at.chunk = chunk; at.scale = 0.125f; at.q_log2 = 1;
         at.out = b.att; at.o_bs = (long long)T * D; at.o_hs = 64; at.o_lo = D; at.n_splits = 1;
         HVX_CHECK(launch_attention(at, s));
-        g = linear(dt, T, D, D, b.att, D, bw[4], (const float*)bw[5]);      // (bf16 operands: the attention writes bf16, which is exact in fp16 — fp16 weights here change nothing)
+        g = linear(dt, T, D, D, b.att, D, bw[4], (const float*)bw[5]);      // (bf16 mode: bf16 operands — the attention writes bf16, which is exact in fp16, so fp16 weights alone change nothing; fp16 mode: fp16 attention output and weights)
         g.batch = B; g.a_bs = (long long)T * D;
         g.gate = mod + 2 * D; g.gate_bs = mbs; g.res = static_cast<const float*>(xs); g.res_f16 = hs; g.res_bs = (long long)T * D; g.ldres = D;
         g.out = xs; g.out_f32 = hs ? 0 : 1; g.out_f16 = hs; g.out_bs = (long long)T * D; g.ldo = D; g.out_cols = D;
@@ -326,6 +333,12 @@ extern "C" {
 
 int hvx_flow_create(const hvx_flow_config* cfg, const void* const* weights, int32_t n_weights, hvx_flow** out) {
     if (!cfg || !weights || !out) return set_error("hvx_flow_create: null argument"), -1;
+    if (cfg->dtype != DT_F32 && cfg->dtype != DT_BF16 && cfg->dtype != DT_F16) return set_error("hvx_flow_create: dtype %d is not 0 (fp32), 1 (bf16) or 2 (fp16)", cfg->dtype), -1;
+    // fp16 mode: the DiT's fp16 GEMMs exist in the 256-tile Linear (gemm_big.hip) and the resident-row convolution (conv_resident.hip) only; the fp32 output
+    // projection's input borrows the FF hidden buffer (ff >= 2 dim)
+    if (cfg->dtype == DT_F16 && (cfg->dim < 256 || (cfg->dim & 63) || (cfg->ff & 63) || cfg->ff < 2 * cfg->dim || cfg->conv_groups <= 0 || cfg->dim != 64 * cfg->conv_groups ||
+                                 cfg->conv_kernel < 2 || cfg->conv_kernel > 33))
+        return set_error("hvx_flow_create: the fp16 mode needs dim >= 256, dim and ff multiples of 64, ff >= 2 dim, 64 channels per conv group and 2..33 conv taps"), -1;
     const int expect = 19 + 10 * cfg->depth + 4;
     if (n_weights != expect) return set_error("hvx_flow_create: expected %d weight pointers, got %d", expect, n_weights), -1;
     if (cfg->dim != cfg->heads * 64 || cfg->dim % cfg->conv_groups || (cfg->dim / cfg->conv_groups) % 32 || cfg->pla_channels % 32 ||

@@ -7,7 +7,8 @@
 
 namespace hvx {
 
-// DT_F16: operands of the DiT block Linears (256-tile form only) and the activations feeding them, when the flow handle runs them in fp16
+// DT_F16: operands of the DiT block Linears (256-tile form only) and the activations feeding them, when the flow handle runs them in fp16; the flow's fp16
+// mode (hvx_flow_config.dtype == 2) also runs the DiT attention (attention.hip: launch_dit_f16) and the position-embedding convolutions (conv_resident.hip) on it
 enum DType : int { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };
 inline size_t dtype_size(int dt) { return dt == DT_F32 ? 4 : 2; }
 
@@ -67,6 +68,9 @@ struct GemmArgs {
     //      its flow decoder in fp16 end to end (infer_speech_model.py:103), i.e. with an fp16 residual stream; here only the stream is fp16 — the
     //      update gate * (acc + bias) + res is formed in fp32 and rounded once on the way out.
     int res_f16; int out_f16;
+    // ---- EPI_QKV_DIT with fp16 operands (gemm_big.hip): q / k / V^T are written as IEEE fp16 (round to nearest, saturated at +-65504) instead of bf16 —
+    //      the attention of the flow's DT_F16 mode reads fp16
+    int qkv_f16;
 };
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 int launch_gemm_x3(const GemmArgs& a, hipStream_t s);    // same convention; fp32 operands on the bf16 matrix cores (GemmArgs.x3)

@@ -147,6 +147,7 @@ extern "C" {
 
 int hvx_llm_create(const hvx_llm_config* cfg, const void* const* weights, int32_t n_weights, hvx_llm** out) {
     if (!cfg || !weights || !out) return set_error("hvx_llm_create: null argument"), -1;
+    if (cfg->dtype != DT_F32 && cfg->dtype != DT_BF16) return set_error("hvx_llm_create: dtype %d: the LLM computes in fp32 (0) or bf16 (1)", cfg->dtype), -1;
     const int expect = 6 + 9 * cfg->layers + 7;
     if (n_weights != expect) return set_error("hvx_llm_create: expected %d weight pointers, got %d", expect, n_weights), -1;
     if (cfg->hidden % 32 || cfg->inter % 128 || (cfg->q_heads * 64) % 128 || cfg->mtp_inter % 16 || cfg->mtp_attn_dim % 32 || cfg->vocab_pad % 16 ||

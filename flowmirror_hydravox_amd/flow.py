@@ -44,15 +44,95 @@ def euler_schedule(n_timesteps):
     return ts, dts
 
 
+FLOW_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def packed_flow_dtype(ws, depth):
+    """The flow mode a packed weight list (HvxFlow.pack_state_dict) was made for.  The tell is the attention out-projection of block 0 (weights[23]): it is
+    packed in the handle's dtype in every mode — fp32, bf16 (also with fp16 block Linears, whose QKV / FF matrices are fp16 while this one stays bf16), fp16."""
+    if depth > 0:
+        return ws[19 + 4].dtype
+    return ws[15].dtype                                    # (no blocks: the position-embedding convolution, also packed in the handle's dtype)
+
+
+def fp16_mode_supported(cfg):
+    """hvx_flow_create's conditions for the fp16 mode (its fp16 GEMMs exist in the 256-tile Linear and the resident-row convolution only)"""
+    return (cfg.dim >= 256 and cfg.dim % 64 == 0 and cfg.ff % 64 == 0 and cfg.ff >= 2 * cfg.dim and cfg.conv_groups > 0 and cfg.dim == 64 * cfg.conv_groups and
+            2 <= cfg.conv_kernel <= 33)
+
+
+def pack_flow_state(cfg, sd, dtype, device, max_t, f16_linears=False, f32_small=False):
+    """reference checkpoint -> the tensors libhvx consumes for a flow handle of `dtype`, in the order include/hvx.h documents (HvxFlow.pack_state_dict;
+    f16_linears / f32_small: the bf16 mode's switches).  fp16 mode: the DiT's block Linears, attention out-projections and position-embedding convolutions in
+    fp16, every other matrix fp32 (small Linears and the pre-lookahead convolutions, as in the fp32 mode)."""
+    sd = {k: v for k, v in sd.items() if k not in DROP_KEYS}
+    fp16 = dtype == torch.float16
+    f32_small = f32_small or fp16
+    check_state(sd, flow_spec(cfg), 'CausalMaskedDiffWithDiT', optional=('decoder.estimator.rotary_embed.inv_freq',))
+    c, dt, dev = cfg, dtype, torch.device(device)
+    e = 'decoder.estimator.'
+
+    def W(k):
+        return sd[k].to(dev).float()
+
+    def mat(t):
+        return t.to(dt).contiguous()
+
+    def emat(t):                                       # a pre-lookahead convolution of the token encoder: fp32 in the fp16 mode
+        return t.float().contiguous() if fp16 else t.to(dt).contiguous()
+
+    def smat(t):                                       # a small Linear of the estimator: fp32 operands when the handle runs them so
+        return t.float().contiguous() if f32_small else t.to(dt).contiguous()
+
+    def lmat(t):                                       # a DiT block Linear: fp16 operands when the handle runs them so
+        return t.to(torch.float16 if f16_linears else dt).contiguous()
+
+    def vec(t):
+        return t.float().contiguous()
+
+    cos, sin = dit_rope_tables(max_t, c.head_dim)
+    melp = (c.mel + 31) // 32 * 32
+    ws = [cos.to(dev), sin.to(dev), vec(W('input_embedding.weight')), vec(W('spk_embed_affine_layer.weight')),
+          vec(W('spk_embed_affine_layer.bias')),
+          emat(conv_weight(W('pre_lookahead_layer.conv1.weight'), melp)), vec(W('pre_lookahead_layer.conv1.bias')),
+          emat(conv_weight(W('pre_lookahead_layer.conv2.weight'))), vec(W('pre_lookahead_layer.conv2.bias')),
+          smat(W(e + 'time_embed.time_mlp.0.weight')), vec(W(e + 'time_embed.time_mlp.0.bias')),
+          smat(W(e + 'time_embed.time_mlp.2.weight')), vec(W(e + 'time_embed.time_mlp.2.bias')),
+          smat(linear_weight(W(e + 'input_embed.proj.weight'))), vec(W(e + 'input_embed.proj.bias')),
+          mat(grouped_conv_weight(W(e + 'input_embed.conv_pos_embed.conv1.0.weight'), c.conv_groups)),
+          vec(W(e + 'input_embed.conv_pos_embed.conv1.0.bias')),
+          mat(grouped_conv_weight(W(e + 'input_embed.conv_pos_embed.conv2.0.weight'), c.conv_groups)),
+          vec(W(e + 'input_embed.conv_pos_embed.conv2.0.bias'))]
+    for i in range(c.depth):
+        p = e + 'transformer_blocks.%d.' % i
+        wqkv = torch.cat([W(p + 'attn.to_q.weight'), W(p + 'attn.to_k.weight'), W(p + 'attn.to_v.weight')], 0)
+        bqkv = torch.cat([W(p + 'attn.to_q.bias'), W(p + 'attn.to_k.bias'), W(p + 'attn.to_v.bias')], 0)
+        ws += [smat(W(p + 'attn_norm.linear.weight')), vec(W(p + 'attn_norm.linear.bias')), lmat(wqkv), vec(bqkv),
+               mat(W(p + 'attn.to_out.0.weight')), vec(W(p + 'attn.to_out.0.bias')),
+               lmat(W(p + 'ff.ff.0.0.weight')), vec(W(p + 'ff.ff.0.0.bias')), lmat(W(p + 'ff.ff.2.weight')), vec(W(p + 'ff.ff.2.bias'))]
+    ws += [smat(W(e + 'norm_out.linear.weight')), vec(W(e + 'norm_out.linear.bias')), smat(W(e + 'proj_out.weight')), vec(W(e + 'proj_out.bias'))]
+    return ws
+
+
 class HvxFlow:
     def __init__(self, cfg: FlowConfig, state_dict=None, dtype=torch.bfloat16, device='cuda', max_t=None, half_stream=None, f16_linears=None, f32_small=None):
+        """dtype: torch.bfloat16 (production: the switches below), torch.float32 (the exact parity mode) or torch.float16 — the reference's deployed dtype
+        (`flow.eval().cuda().half()`, infer_speech_model.py:103) with ONE fixed arithmetic and no switches: every matrix-core operand of the DiT (block Linears,
+        the attention's out-projection, q / k / V^T and the probabilities, the position-embedding convolutions) in IEEE fp16, the residual stream, the small
+        Linears, the token encoder and the solver state in fp32 — within 1e-3 of the fp32 reference (tools/flow_fp16_study.py, tests/test_gpu_flow_fp16.py)."""
+        if dtype not in FLOW_DTYPES:
+            raise _lib.HvxError('HvxFlow computes in fp32, bf16 or fp16, not %s' % dtype)
+        if dtype == torch.float16 and not fp16_mode_supported(cfg):
+            raise _lib.HvxError('the fp16 flow mode needs dim >= 256, dim and ff multiples of 64, ff >= 2 dim, 64 channels per conv group and 2..33 conv taps')
+        if dtype == torch.float16 and any(v for v in (half_stream, f16_linears, f32_small) if v is not None):
+            raise ValueError('half_stream / f16_linears / f32_small belong to the bf16 mode: the fp16 mode has one fixed arithmetic')
         _lib.require_gpu()
         self.lib = _lib.load()
         self.cfg = cfg
         self.dtype = dtype
         self.device = torch.device(device)
         self.bf16 = dtype == torch.bfloat16
-        self.fp16 = False
+        self.fp16 = dtype == torch.float16                 # (the reference's loader attribute: the decoder runs `.half()`)
         # bf16 mode: the DiT's residual stream is kept in fp16, the arithmetic the reference itself runs (`flow.eval().cuda().half()`,
         # infer_speech_model.py:103); half_stream=False keeps it in fp32 (the fp32 mode always does).  HVX_FLOW_HALF_STREAM=0/1 overrides.
         if half_stream is None:
@@ -88,51 +168,13 @@ class HvxFlow:
 
     def pack_state_dict(self, sd):
         """reference checkpoint -> the device tensors libhvx consumes, in the order include/hvx.h documents"""
-        sd = {k: v for k, v in sd.items() if k not in DROP_KEYS}
-        check_state(sd, flow_spec(self.cfg), 'CausalMaskedDiffWithDiT', optional=('decoder.estimator.rotary_embed.inv_freq',))
-        c, dt, dev = self.cfg, self.dtype, self.device
-        e = 'decoder.estimator.'
-
-        def W(k):
-            return sd[k].to(dev).float()
-
-        def mat(t):
-            return t.to(dt).contiguous()
-
-        def smat(t):                                       # a small Linear of the estimator: fp32 operands when the handle runs them so
-            return t.float().contiguous() if self.f32_small else t.to(dt).contiguous()
-
-        def lmat(t):                                       # a DiT block Linear: fp16 operands when the handle runs them so
-            return t.to(torch.float16 if self.f16_linears else dt).contiguous()
-
-        def vec(t):
-            return t.float().contiguous()
-
-        cos, sin = dit_rope_tables(self.max_t, c.head_dim)
-        melp = (c.mel + 31) // 32 * 32
-        ws = [cos.to(dev), sin.to(dev), vec(W('input_embedding.weight')), vec(W('spk_embed_affine_layer.weight')),
-              vec(W('spk_embed_affine_layer.bias')),
-              mat(conv_weight(W('pre_lookahead_layer.conv1.weight'), melp)), vec(W('pre_lookahead_layer.conv1.bias')),
-              mat(conv_weight(W('pre_lookahead_layer.conv2.weight'))), vec(W('pre_lookahead_layer.conv2.bias')),
-              smat(W(e + 'time_embed.time_mlp.0.weight')), vec(W(e + 'time_embed.time_mlp.0.bias')),
-              smat(W(e + 'time_embed.time_mlp.2.weight')), vec(W(e + 'time_embed.time_mlp.2.bias')),
-              smat(linear_weight(W(e + 'input_embed.proj.weight'))), vec(W(e + 'input_embed.proj.bias')),
-              mat(grouped_conv_weight(W(e + 'input_embed.conv_pos_embed.conv1.0.weight'), c.conv_groups)),
-              vec(W(e + 'input_embed.conv_pos_embed.conv1.0.bias')),
-              mat(grouped_conv_weight(W(e + 'input_embed.conv_pos_embed.conv2.0.weight'), c.conv_groups)),
-              vec(W(e + 'input_embed.conv_pos_embed.conv2.0.bias'))]
-        for i in range(c.depth):
-            p = e + 'transformer_blocks.%d.' % i
-            wqkv = torch.cat([W(p + 'attn.to_q.weight'), W(p + 'attn.to_k.weight'), W(p + 'attn.to_v.weight')], 0)
-            bqkv = torch.cat([W(p + 'attn.to_q.bias'), W(p + 'attn.to_k.bias'), W(p + 'attn.to_v.bias')], 0)
-            ws += [smat(W(p + 'attn_norm.linear.weight')), vec(W(p + 'attn_norm.linear.bias')), lmat(wqkv), vec(bqkv),
-                   mat(W(p + 'attn.to_out.0.weight')), vec(W(p + 'attn.to_out.0.bias')),
-                   lmat(W(p + 'ff.ff.0.0.weight')), vec(W(p + 'ff.ff.0.0.bias')), lmat(W(p + 'ff.ff.2.weight')), vec(W(p + 'ff.ff.2.bias'))]
-        ws += [smat(W(e + 'norm_out.linear.weight')), vec(W(e + 'norm_out.linear.bias')), smat(W(e + 'proj_out.weight')), vec(W(e + 'proj_out.bias'))]
-        return ws
+        return pack_flow_state(self.cfg, sd, self.dtype, self.device, self.max_t, f16_linears=self.f16_linears, f32_small=self.f32_small)
 
     def load_packed(self, ws):
         c, dt, dev = self.cfg, self.dtype, self.device
+        got = packed_flow_dtype(ws, c.depth)
+        if got != dt:
+            raise ValueError('packed flow weights were made for the %s mode, this handle runs %s' % (got, dt))
         ws = [w.to(dev) for w in ws]
         self._weights = ws
         if self.bf16 and c.depth > 0:
@@ -144,6 +186,7 @@ class HvxFlow:
                              conv_groups=c.conv_groups, time_freq_dim=c.time_freq_dim, max_t=self.max_t, cfg_rate=c.cfg_rate)
         if self._h is not None:
             self.lib.hvx_flow_destroy(self._h)
+            self._h = None
         h = C.c_void_p()
         check(self.lib.hvx_flow_create(C.byref(cc), _lib.ptr_array(ws), len(ws), C.byref(h)), 'hvx_flow_create')
         self._h = h

@@ -58,6 +58,8 @@ class HvxLLM:
         code x scale exactly — and wide bf16 decode grids stream the codes instead (hvx_llm_set_head_mlp_fp8: half the bytes, bit-identical
         log-probabilities); the packed cache keeps the codes only.  A second numerical contract for the heads (tests/test_gpu_cv3w.py states the
         id agreement with the bf16 heads), hence off by default."""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.HvxError('HvxLLM computes in bf16 or fp32, not %s (fp16 is a flow mode: HvxFlow(dtype=torch.float16))' % dtype)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.cfg = cfg

@@ -54,8 +54,15 @@ def _load_pt(path):
     return sd
 
 
+def _env_on(name):
+    return os.environ.get(name, '').strip().lower() in ('1', 'true', 'yes', 'on')
+
+
 class HvxModelManager:
-    def __init__(self, frontend_factory=None):
+    def __init__(self, frontend_factory=None, flow_fp16=None):
+        """flow_fp16: run the flow decoder in its fp16 mode (HvxFlow(dtype=torch.float16): within 1e-3 of the fp32 reference, the reference's own deployed
+        dtype) instead of the bf16 production mode; None = $HVX_FLOW_FP16 (default off)."""
+        self.flow_fp16 = _env_on('HVX_FLOW_FP16') if flow_fp16 is None else bool(flow_fp16)
         self.models = None
         self.frontend = None
         self.configs = None
@@ -77,7 +84,7 @@ class HvxModelManager:
         # precision policy of the reference (:101-118): llm bf16 / flow half / hift fp32.  fp16 requests run in bf16 as well:
         # libhvx computes in bf16 (or fp32), with fp32 accumulation and an fp32 residual stream.
         # optional fp8 head weights (llm.HvxLLM: head_mlp_fp8): args.head_fp8 or $HVX_HEAD_FP8=1
-        head_fp8 = bool(getattr(args, 'head_fp8', False)) or os.environ.get('HVX_HEAD_FP8', '').strip().lower() in ('1', 'true', 'yes', 'on')
+        head_fp8 = bool(getattr(args, 'head_fp8', False)) or _env_on('HVX_HEAD_FP8')
         llm = HvxLLM(cfg.llm, None, dtype=torch.bfloat16, head_mlp_fp8=head_fp8)
         if extras.get('sampling'):                           # the yaml's `sampling: !name:...ras_sampling` keyword defaults
             from functools import partial
@@ -85,7 +92,8 @@ class HvxModelManager:
             llm.sampling = partial(ras_sampling, **extras['sampling'])
         if extras.get('inference_head_num'):
             llm.inference_head_num = int(extras['inference_head_num'])
-        flow = HvxFlow(cfg.flow, None, dtype=torch.bfloat16)
+        # flow: bf16 production mode, or the fp16 mode on request (constructor flow_fp16 / $HVX_FLOW_FP16=1)
+        flow = HvxFlow(cfg.flow, None, dtype=torch.float16 if self.flow_fp16 else torch.bfloat16)
         hift = HvxHift(cfg.hift, None)
         # optional packed-weight cache: args.packed_cache or $HVX_PACKED_CACHE names a directory that holds the
         # device-ready tensors of each `.pt` (checkpoint.py); without it the `.pt` files are read and packed on every start
@@ -93,7 +101,7 @@ class HvxModelManager:
         self.load_report = {}
         for name, model in (('llm', llm), ('flow', flow), ('hift', hift)):
             self.load_report[name] = self._load_into(model, os.path.join(args.model_dir, name + '.pt'))
-        llm.bf16, flow.bf16, llm.fp16, flow.fp16 = True, True, False, False
+        llm.bf16, flow.bf16, llm.fp16, flow.fp16 = True, not self.flow_fp16, False, self.flow_fp16
         self.models = {'llm': llm, 'flow': flow, 'hift': hift}
         self.configs = {'sample_rate': cfg.sample_rate}
         if self._frontend_factory is not None:
@@ -115,7 +123,7 @@ class HvxModelManager:
             self._load_into(self.models['llm'], llm_pt)
             self.models['llm'].bf16, self.models['llm'].fp16 = True, False
             self._load_into(self.models['flow'], flow_pt)
-            self.models['flow'].bf16, self.models['flow'].fp16 = True, False
+            self.models['flow'].bf16, self.models['flow'].fp16 = not self.flow_fp16, self.flow_fp16
             return {'status': 'success', 'message': 'model weights loaded'}
         except Exception as e:                               # never raises (:181-184)
             logger.error('load_pt failed: %s', e)

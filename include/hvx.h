@@ -25,6 +25,7 @@ extern "C" {
 #define HVX_ABI_VERSION 4
 #define HVX_F32 0
 #define HVX_BF16 1
+#define HVX_F16 2                         /* IEEE fp16: hvx_flow_config.dtype only (the flow's fp16 mode) */
 
 typedef void* hvx_stream;                 /* hipStream_t */
 
@@ -210,7 +211,7 @@ int hvx_llm_last_hidden(hvx_llm* h, hvx_stream s, int32_t n_seq, float* out);
  * (cosyvoice/flow/flow_matching.py:204-228, 71-124) and DiT.forward (cosyvoice/flow/DiT/dit.py:145-176).
  * ------------------------------------------------------------------------------------------------- */
 typedef struct {
-    int32_t dtype;
+    int32_t dtype;                                /* HVX_F32, HVX_BF16 or HVX_F16 (see the weight dtypes below) */
     int32_t vocab, mel, spk_dim, pla_channels, pla_len;
     int32_t dim, depth, heads, ff, conv_kernel, conv_groups, time_freq_dim;
     int32_t max_t;                                /* rows of the rope tables */
@@ -222,7 +223,12 @@ typedef struct {
  *   9 time_mlp.0 W [D][256] 10 b  11 time_mlp.2 W [D][D] 12 b   13 input proj W [D][320] 14 b
  *   15 conv_pos 1 W [groups][Cg][k*Cg] 16 b [D]  17 conv_pos 2 W  18 b
  *   per block, 10 entries from 19+10i: adaLN W [6D][D], b; Wqkv [3D][D], bqkv; Wout [D][D], b; ff1 W [ff][D], b; ff2 W [D][ff], b
- *   tail: norm_out W [2D][D], b; proj_out W [mel][D], b                                                             */
+ *   tail: norm_out W [2D][D], b; proj_out W [mel][D], b
+ * dtype HVX_F16 (the fp16 mode: every matrix-core operand of the DiT blocks, the attention and the position-embedding convolutions in IEEE fp16 — conversions
+ * round to nearest and saturate at +-65504 —, the residual stream and everything else in fp32): matrices 15, 17 and 19 + 10 i + {2, 4, 6, 8} are fp16; the
+ * matrices 5, 7, 9, 11, 13, 19 + 10 i + 0, 19 + 10 depth + {0, 2} are f32.  Needs dim >= 256, dim and ff multiples of 64, ff >= 2 dim, 64 channels per
+ * position-embedding conv group and 2..33 taps.  hvx_flow_set_half_stream / set_f16_linears / set_f32_small with on != 0 are refused on such a handle
+ * (its arithmetic is fixed).                                                                                        */
 typedef struct hvx_flow hvx_flow;
 int hvx_flow_create(const hvx_flow_config* cfg, const void* const* weights, int32_t n_weights, hvx_flow** out);
 void hvx_flow_destroy(hvx_flow* h);
