@@ -43,7 +43,10 @@ class GemmArgs(C.Structure):
                 ('scale', c_f32),
                 ('out', c_vp), ('out_f32', c_i32), ('out_bs', c_i64), ('ldo', c_i32), ('out_row_off', c_i32), ('out_cols', c_i32),
                 ('out2', c_vp), ('act2', c_i32), ('act2_param', c_f32), ('act2_alpha', c_vp), ('out2_bs', c_i64),
-                ('ldo2', c_i32), ('out2_row_off', c_i32), ('out2_cols', c_i32), ('x3', c_i32), ('res_f16', c_i32), ('out_f16', c_i32)]
+                ('ldo2', c_i32), ('out2_row_off', c_i32), ('out2_cols', c_i32), ('x3', c_i32), ('res_f16', c_i32), ('out_f16', c_i32),
+                ('a_planes', c_i32), ('a_plane', c_i64), ('w_planes', c_i32), ('w_plane', c_i64),
+                ('out_planes', c_i32), ('out_plane', c_i64), ('out2_planes', c_i32), ('out2_plane', c_i64),
+                ('res2', c_vp), ('res2_bs', c_i64), ('ldres2', c_i32), ('div', c_f32)]
 
 
 class AttnArgs(C.Structure):
@@ -119,6 +122,7 @@ SYMBOLS = {
     'hvx_prof_read': (c_i32, [c_i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(C.c_double)]),
     'hvx_ras_sample': (c_i32, [C.POINTER(SampleArgs), c_vp]),
     'hvx_op_gemm': (c_i32, [C.POINTER(GemmArgs), c_vp]),
+    'hvx_op_act_rows': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i64, c_i32, c_f32, c_vp, c_i64, c_i32, c_vp]),
     'hvx_op_attention': (c_i32, [C.POINTER(AttnArgs), c_vp]),
     'hvx_op_resample_linear': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp]),
     'hvx_op_skinny_gemm': (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
@@ -182,8 +186,9 @@ SYMBOLS = {
 
 # include/hvx.h: HVX_ABI_VERSION — bumped whenever a symbol is added or an argument struct changes size / meaning (2: round 4's six symbols, larger
 # SkinnyArgs / AttnArgs, fragment-order KV cache; 3: round 5; 4: round 6 — hvx_set_option / hvx_get_option / hvx_option_name / hvx_build_flags / hvx_is_lab_build,
-# `exact_fp32` in hvx_hift_config and hvx_hifigan_config)
-HVX_ABI_VERSION = 4
+# `exact_fp32` in hvx_hift_config and hvx_hifigan_config; 5: the plane-pair / res2 / div fields of hvx_gemm_args and hvx_op_act_rows, for the parity tests of the
+# vocoder's plane-pair convolutions)
+HVX_ABI_VERSION = 5
 
 _lib = None
 

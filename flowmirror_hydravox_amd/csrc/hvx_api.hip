@@ -115,6 +115,7 @@ int hvx_set_option(const char* key, int64_t value) {
     if (i == OPT_ATT_CHUNK && value != 0 && (value < 128 || value % 128)) return set_error("hvx_set_option: att_chunk must be 0 or a multiple of 128, got %lld", (long long)value), -1;
     if (i == OPT_GEMM_BIG_MFMA && value != 16 && value != 32) return set_error("hvx_set_option: gemm_big_mfma must be 16 or 32, got %lld", (long long)value), -1;
     if (i == OPT_DEC_FUSE_ROWS && (value < 0 || value > 256)) return set_error("hvx_set_option: dec_fuse_rows must be 0..256, got %lld", (long long)value), -1;
+    if ((i == OPT_X3P8 || i == OPT_CONV_RESIDENT || i == OPT_CONV64_RESIDENT) && value != 0 && value != 1) return set_error("hvx_set_option: %s must be 0 or 1, got %lld", key, (long long)value), -1;
     if (i == OPT_ATT_WAVES && value != 4 && value != 8) return set_error("hvx_set_option: att_waves must be 4 or 8, got %lld", (long long)value), -1;
     #ifdef HVX_LAB
     const bool form_ok = value == 0 || value == 16 || value == 17 || value == 32 || value == 48;
@@ -237,8 +238,18 @@ int hvx_op_gemm(const hvx_gemm_args* a, hvx_stream s) {
     g.out2 = a->out2; g.act2 = a->act2; g.act2_param = a->act2_param; g.act2_alpha = a->act2_alpha; g.out2_bs = a->out2_bs;
     g.ldo2 = a->ldo2; g.out2_row_off = a->out2_row_off; g.out2_cols = a->out2_cols; g.x3 = a->x3;
     g.res_f16 = a->res_f16; g.out_f16 = a->out_f16;
+    g.a_planes = a->a_planes; g.a_plane = a->a_plane; g.w_planes = a->w_planes; g.w_plane = a->w_plane;
+    g.out_planes = a->out_planes; g.out_plane = a->out_plane; g.out2_planes = a->out2_planes; g.out2_plane = a->out2_plane;
+    g.res2 = a->res2; g.res2_bs = a->res2_bs; g.ldres2 = a->ldres2; g.div = a->div;
     if (g.out_f16 && g.out_f32) return set_error("hvx_op_gemm: out_f16 and out_f32 are exclusive"), -1;
     return launch_gemm(g, (hipStream_t)s);
+}
+
+int hvx_op_act_rows(const float* x, int32_t ldx, void* y, int32_t ldy, int32_t planes, int64_t plane, int32_t act, float act_param, const float* alpha,
+                    int64_t rows, int32_t cols, hvx_stream s) {
+    if (!x || !y) return set_error("hvx_op_act_rows: null argument"), -1;
+    if (planes) return launch_act_rows_planes(x, ldx, y, ldy, plane, act, act_param, alpha, rows, cols, (hipStream_t)s);
+    return launch_act_rows(x, ldx, y, ldy, DT_F32, act, act_param, alpha, rows, cols, (hipStream_t)s);
 }
 
 int hvx_op_attention(const hvx_attn_args* a, hvx_stream s) {

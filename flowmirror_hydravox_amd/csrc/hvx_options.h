@@ -1,6 +1,6 @@
 // hvx_options.h — the library's run-time options: ONE mechanism, visible to the C-ABI caller (hvx_set_option / hvx_get_option / hvx_option_name in
 // include/hvx.h), instead of environment variables read through function-local statics.  None of them changes a result's CONTRACT: they pick between forms
-// the parity tests hold to each other (dec_gemm, conv64_resident, x3p8, ...) or tune a launch geometry.  Numerics that a caller may care about are NOT here:
+// the parity tests hold to each other (dec_gemm: tests/test_gpu_fullsize.py; conv64_resident, x3p8: tests/test_gpu_planes.py, operator by operator) or tune a launch geometry.  Numerics that a caller may care about are NOT here:
 // the vocoder's exact-fp32 form is a field of hvx_hift_config / hvx_hifigan_config.  Options marked `lab` exist for timing studies (tools/): the shipped
 // library refuses to set them — they are settable only in a library compiled with -DHVX_LAB (python -m flowmirror_hydravox_amd.build --lab ...).
 // Values are read at dispatch time (an atomic load per launch decision); a captured step graph keeps the forms it was captured with.
@@ -19,6 +19,7 @@ enum OptId : int {
     OPT_GEMM_BIG_MIN_TILES,    // fewest 256 x 256 tiles for which the 256-tile Linear is chosen over the 128-tile one
     OPT_DEC_GEMM,              // 1: 33..256-row decode grids on gemm_dec.hip (fragment-order activations); 0: the generic skinny kernels (the tests compare the two)
     OPT_DEC_HEADS,             // bit 0: MTP head MLPs, bit 1: the shared output projection on gemm_dec.hip
+    // (conv_resident, conv64_resident and x3p8 select a kernel form: hvx_set_option refuses any value but 0 / 1)
     OPT_CONV_RESIDENT,         // 1: the DiT position embedding's 64-channel grouped convolution in the resident-row form; 0: tiled
     OPT_CONV64_RESIDENT,       // 1: the vocoder's 64-channel split-bf16 convolutions in the resident-row form; 0: tiled (the tests compare the two)
     OPT_X3P8,                  // 1: the 8-wave 128 x 128 x 64 tile for the vocoder's 128- / 256-channel split-bf16 convolutions; 0: the 4-wave tile

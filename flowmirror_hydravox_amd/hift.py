@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import check, ptr, stream_ptr
 from .config import HiftConfig
-from .packing import conv_weight, fold_weight_norm, pad_to
+from .packing import conv_weight, fold_weight_norm, pad_to, split_planes
 from .weights import hift_spec, check_state, DROP_KEYS, hift_source_down_rates
 
 
@@ -132,9 +132,7 @@ class HvxHift:
         self._planes = []
         for k, w in enumerate(ws):
             if k >= 14 and w.dim() == 2 and k not in skip:
-                hi = w.to(torch.bfloat16)
-                lo = (w - hi.float()).to(torch.bfloat16)
-                self._planes.append(torch.stack([hi, lo]).contiguous())
+                self._planes.append(split_planes(w))
             else:
                 self._planes.append(None)
         arr = (C.c_void_p * len(ws))(*[None if p is None else p.data_ptr() for p in self._planes])

@@ -105,6 +105,15 @@ def conv_weight(w, cin_pad=None):
     return o.reshape(cout, k * cp).contiguous()
 
 
+def split_planes(x):
+    """fp32 tensor -> bf16 [2][...]: the (hi, lo) plane pair of csrc/hvx_kernels.h (GemmArgs.a_planes): hi = bf16(x), lo = bf16(x - float(hi)), both round to
+    nearest even; x == hi + lo up to 2^-17 |x|."""
+    x = x.to(torch.float32)
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    return torch.stack([hi, lo]).contiguous()
+
+
 def grouped_conv_weight(w, groups):
     """[D][Cg][k] (groups blocks of Cg output channels) -> [groups][Cg][k*Cg]."""
     D, cg, k = w.shape

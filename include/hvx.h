@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define HVX_ABI_VERSION 4
+#define HVX_ABI_VERSION 5
 #define HVX_F32 0
 #define HVX_BF16 1
 #define HVX_F16 2                         /* IEEE fp16: hvx_flow_config.dtype only (the flow's fp16 mode) */
@@ -98,9 +98,23 @@ typedef struct {
     int32_t x3;   /* fp32 only: allow the split-bf16 form (each operand as a bf16 pair, three bf16 MFMAs per step; ~1e-6 relative) */
     int32_t res_f16;   /* res holds IEEE fp16 instead of fp32 (same strides, in elements): the DiT's half residual stream, hvx_flow_set_half_stream */
     int32_t out_f16;   /* out holds IEEE fp16 (out_f32 must be 0) */
+    /* fp32 values as (hi, lo) bf16 PLANE PAIRS (dtype HVX_F32): hi = bf16(x), lo = bf16(x - hi), x == hi + lo up to 2^-17 |x|.  A pair is addressed like the fp32
+     * tensor it stands for (same row / batch strides, in elements), the lo plane `*_plane` bf16 elements behind the hi plane.  a_planes and w_planes (both or
+     * neither) select the plane-pair convolution kernels of the vocoder; out_planes / out2_planes make the epilogue write a pair instead of fp32 values. */
+    int32_t a_planes; int64_t a_plane;
+    int32_t w_planes; int64_t w_plane;
+    int32_t out_planes; int64_t out_plane;
+    int32_t out2_planes; int64_t out2_plane;
+    const float* res2; int64_t res2_bs; int32_t ldres2;   /* second fp32 residual, read at row m (no row offset) */
+    float div;         /* != 0: the value is divided by it after `scale` (the mean over the ResBlocks of a vocoder stage) */
 } hvx_gemm_args;
 /* implicit-GEMM Conv1d / Linear on MFMA (torch.nn.functional.conv1d / linear call sites of the path) */
 int hvx_op_gemm(const hvx_gemm_args* a, hvx_stream s);
+
+/* y[r, c] = act(x[r, c]) for an fp32 [rows][cols] matrix (per-column alpha for Snake; alpha may be null): the Snake in front of every vocoder ResBlock.
+ * planes != 0: y is a (hi, lo) bf16 plane pair, the lo plane `plane` elements behind hi (cols, ldx, ldy, plane multiples of 4); else y is fp32. */
+int hvx_op_act_rows(const float* x, int32_t ldx, void* y, int32_t ldy, int32_t planes, int64_t plane, int32_t act, float act_param, const float* alpha,
+                    int64_t rows, int32_t cols, hvx_stream s);
 
 typedef struct {
     int32_t dtype, batch, heads, t, t_pad;     /* q,k: [b][h][t_pad][64]; vT: [b][h][64][t_pad]; out: [b][t][h*64] */

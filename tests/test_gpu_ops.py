@@ -59,9 +59,11 @@ def _rows(x_bct, dtype, cpad=None):
 
 @pytest.mark.parametrize('cin,cout,k,dil,T', [(512, 512, 3, 5, 40000), (128, 64, 7, 1, 9000), (256, 256, 11, 3, 33000)])
 def test_conv_split_bf16_form_matches_fp64(cin, cout, k, dil, T):
-    """gemm_x3.hip: an fp32 convolution computed on the bf16 matrix cores from (hi, lo) bf16 pairs of both operands, three MFMAs per
-    step.  Bound against an fp64 convolution: 2e-5 of the output scale (the exact fp32 MFMA form sits at ~1e-6; the vocoder contract
-    is 1e-3).  Shapes of the HiFT resblocks (dilated, left-padded), Snake epilogue and residual included."""
+    """gemm_x3.hip, gemm_x3_kernel (the IN-KERNEL split: fp32 operands, split into (hi, lo) bf16 pairs on their way into LDS, three MFMAs per
+    step).  Bound against an fp64 convolution: 2e-5 of the output scale (the exact fp32 MFMA form sits at ~1e-6; the vocoder contract
+    is 1e-3).  Shapes of the HiFT resblocks (dilated, left-padded), Snake epilogue and residual included.  In the product this kernel runs the
+    vocoder's source down-sampling convolutions, and conv_pre / every decode convolution when no weight planes were handed over; the default
+    decode convolutions read plane pairs through other kernels (gemm_x3p_kernel, gemm_x3p8_kernel, conv64_x3p_kernel): tests/test_gpu_planes.py."""
     _lib, ops, packing = _mods()
     x = _rand(1, cin, T, seed=41)
     w = _rand(cout, cin, k, seed=42) / math.sqrt(cin * k)
@@ -82,9 +84,10 @@ def test_conv_split_bf16_form_matches_fp64(cin, cout, k, dil, T):
 
 @pytest.mark.parametrize('cin,cout,k,dil,T', [(512, 512, 3, 3, 40003), (64, 64, 7, 1, 70001)])
 def test_conv_split_bf16_resblock_modes(cin, cout, k, dil, T):
-    """The two compile-time epilogue modes the HiFT ResBlocks launch on gemm_x3.hip (gemm_epilogue.h, LEAN 2): convs1 = Snake(conv + b) -> fp32,
-    convs2 = conv + b + residual -> fp32 plus Snake of that as the second output (the next block's input); both vocoder tile forms, ragged last
-    row tile, against fp64."""
+    """gemm_x3.hip, gemm_x3_kernel (the in-kernel split of fp32 operands) with the two compile-time epilogue modes of gemm_epilogue.h (LEAN 2) on FP32
+    outputs: convs1 = Snake(conv + b) -> fp32, convs2 = conv + b + residual -> fp32 plus Snake of that as the second output; both of its tile forms,
+    ragged last row tile, against fp64.  The product launches this kernel for the source down-sampling convolutions (and for conv_pre / the ResBlocks
+    only when weight planes are absent); what the default ResBlocks launch — plane-pair operands and plane-pair outputs — is tests/test_gpu_planes.py."""
     _lib, ops, packing = _mods()
     x = _rand(1, cin, T, seed=51)
     w = _rand(cout, cin, k, seed=52) / math.sqrt(cin * k)

@@ -39,7 +39,7 @@ def test_library_builds_and_exports_every_declared_symbol():
         assert hasattr(lib, name), 'libhvx.so does not export %s' % name
     # the ctypes binding covers exactly the header
     assert sorted(_lib.SYMBOLS.keys()) == declared
-    assert _lib.load().hvx_abi_version() == _lib.HVX_ABI_VERSION == 4
+    assert _lib.load().hvx_abi_version() == _lib.HVX_ABI_VERSION == 5
 
 
 def test_libhvx_holds_no_packed_fp32_instruction(tmp_path):
@@ -924,7 +924,8 @@ def test_library_options_are_one_switchboard_and_lab_ones_are_refused():
         assert _lib.get_option('attn_dit_form') == 16 and _lib.get_option('dec_fuse_rows') == 16
     assert _lib.get_option('attn_dit_form') == 0 and _lib.get_option('dec_fuse_rows') == 0
     for key, val, msg in (('no_such_option', 1, 'unknown option'), ('att_chunk', 100, 'multiple of 128'), ('att_waves', 5, '4 or 8'), ('attn_lab', 3, 'lab option'),
-                          ('attn_dit_form', 18, '0, 16, 17 or 32'), ('attn_dit_form', 48, 'lab builds only'), ('dec_fuse_rows', 300, '0..256')):
+                          ('attn_dit_form', 18, '0, 16, 17 or 32'), ('attn_dit_form', 48, 'lab builds only'), ('dec_fuse_rows', 300, '0..256'),
+                          ('x3p8', 2, 'x3p8 must be 0 or 1'), ('conv64_resident', -1, 'conv64_resident must be 0 or 1'), ('conv_resident', 8, 'conv_resident must be 0 or 1')):
         with pytest.raises(_lib.HvxError, match=msg):
             _lib.set_option(key, val)
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'flowmirror_hydravox_amd', 'csrc')
