@@ -56,6 +56,29 @@ class AttnArgs(C.Structure):
                 ('n_splits', c_i32), ('split_chunk', c_i32), ('part_o', c_vp), ('part_ml', c_vp), ('chunk', c_i32), ('q_log2', c_i32)]
 
 
+class DecodeGemmArgs(C.Structure):
+    _fields_ = [('form', c_i32), ('dtype', c_i32), ('M', c_i32), ('N', c_i32), ('K', c_i32),
+                ('A', c_vp), ('lda', c_i32), ('W', c_vp), ('split_k', c_i32), ('epi', c_i32), ('bias', c_vp), ('part', c_vp),
+                ('out', c_vp), ('out_f32', c_i32), ('ldo', c_i32), ('out2', c_vp), ('ldo2', c_i32),
+                ('kn', c_i32), ('q_heads', c_i32), ('kv_heads', c_i32), ('slot', c_vp), ('pos0', c_vp), ('n_new', c_vp),
+                ('rope_cos', c_vp), ('rope_sin', c_vp), ('qbuf', c_vp), ('kcache', c_vp), ('vTcache', c_vp),
+                ('max_ctx', c_i32), ('kv_frag', c_i32),
+                ('nz', c_i32), ('w_zs', c_i64), ('a_zs', c_i64), ('bias_zs', c_i64), ('out_zs', c_i64), ('part_zs', c_i64),
+                ('n_valid', c_i32), ('a_norm', c_i32), ('norm_eps', c_f32), ('a_frag', c_i32), ('out_frag', c_i32),
+                ('w_fp8', c_i32), ('w_scale', c_vp), ('w_scale_zs', c_i64)]
+
+
+class ReduceNormArgs(C.Structure):
+    _fields_ = [('x', c_vp), ('ldx', c_i32), ('part', c_vp), ('split_k', c_i32), ('part_stride', c_i64), ('part_zs', c_i64),
+                ('bias', c_vp), ('bias_zs', c_i64), ('gain', c_vp), ('gain_zs', c_i64), ('eps', c_f32), ('do_norm', c_i32),
+                ('y', c_vp), ('ldy', c_i32), ('dtype', c_i32), ('M', c_i32), ('H', c_i32), ('rows_per_z', c_i32),
+                ('y_frag', c_i32), ('y_frag_zrows', c_i32)]
+
+
+# SkinnyEpi (csrc/hvx_kernels.h): the epilogues of the decode GEMMs
+SK_PARTIAL, SK_STORE, SK_QKV_ROPE, SK_SWIGLU, SK_RESID = range(5)
+
+
 class FeatureConfig(C.Structure):
     _fields_ = [('frame_len', c_i32), ('hop', c_i32), ('reflect_pad', c_i32), ('n_frames', c_i32), ('bins', c_i32), ('power', c_i32), ('mag_eps', c_f32),
                 ('n_mels', c_i32), ('log_floor', c_f32), ('log_scale', c_f32), ('post', c_i32), ('time_major', c_i32)]
@@ -126,6 +149,8 @@ SYMBOLS = {
     'hvx_op_attention': (c_i32, [C.POINTER(AttnArgs), c_vp]),
     'hvx_op_resample_linear': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp]),
     'hvx_op_skinny_gemm': (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
+    'hvx_op_decode_gemm': (c_i32, [C.POINTER(DecodeGemmArgs), c_vp]),
+    'hvx_op_reduce_rmsnorm': (c_i32, [C.POINTER(ReduceNormArgs), c_vp]),
     'hvx_llm_create': (c_i32, [C.POINTER(LLMConfig), C.POINTER(c_vp), c_i32, C.POINTER(c_vp)]),
     'hvx_llm_destroy': (None, [c_vp]),
     'hvx_llm_workspace_bytes': (c_sz, [c_vp, c_i32, c_i32, c_i32]),
@@ -187,8 +212,9 @@ SYMBOLS = {
 # include/hvx.h: HVX_ABI_VERSION — bumped whenever a symbol is added or an argument struct changes size / meaning (2: round 4's six symbols, larger
 # SkinnyArgs / AttnArgs, fragment-order KV cache; 3: round 5; 4: round 6 — hvx_set_option / hvx_get_option / hvx_option_name / hvx_build_flags / hvx_is_lab_build,
 # `exact_fp32` in hvx_hift_config and hvx_hifigan_config; 5: the plane-pair / res2 / div fields of hvx_gemm_args and hvx_op_act_rows, for the parity tests of the
-# vocoder's plane-pair convolutions)
-HVX_ABI_VERSION = 5
+# vocoder's plane-pair convolutions; 6: hvx_op_decode_gemm / hvx_op_reduce_rmsnorm, for the parity tests of the decode GEMMs, and the dec_gpw_* options settable
+# in the shipped library)
+HVX_ABI_VERSION = 6
 
 _lib = None
 

@@ -409,7 +409,7 @@ int launch_dec_gemm(const SkinnyArgs& a_in, hipStream_t s) {
     // (gate, up) pairs for the MLP (102 x 2 workgroups: the activation re-reads of more, smaller workgroups cost more than the idle CUs), two
     // pairs of tiles per K slice for the down projection (14 x 8 x 2)
     const int gpw_qkv = (int)opt(OPT_DEC_GPW_QKV), gpw_res = (int)opt(OPT_DEC_GPW_RES), gpw_mlp = (int)opt(OPT_DEC_GPW_MLP),
-              gpw_down = (int)opt(OPT_DEC_GPW_DOWN), gpw_out = (int)opt(OPT_DEC_GPW_OUT), gpw_hmlp = (int)opt(OPT_DEC_GPW_HMLP);       // (lab options: the defaults are the tuned values)
+              gpw_down = (int)opt(OPT_DEC_GPW_DOWN), gpw_out = (int)opt(OPT_DEC_GPW_OUT), gpw_hmlp = (int)opt(OPT_DEC_GPW_HMLP);       // (options dec_gpw_*: the defaults are the tuned values)
     switch (a.epi) {
         case SK_QKV_ROPE:
             if (a.N != (a.q_heads + 2 * a.kv_heads) * 64) return set_error("launch_dec_gemm: QKV width %d != (q+2kv)*64", a.N), -1;

@@ -60,7 +60,8 @@ void prof_end(int slot, hipStream_t s) {
 const OptDef g_opt_defs[OPT_COUNT] = {
     {"att_chunk", 0, 0}, {"att_waves", 8, 0}, {"gemm_big_gw", 4, 0}, {"gemm_big_min_tiles", 128, 0}, {"dec_gemm", 1, 0}, {"dec_heads", 3, 0},
     {"conv_resident", 1, 0}, {"conv64_resident", 1, 0}, {"x3p8", 1, 0}, {"attn_dit_form", 0, 0}, {"dec_fuse_rows", 0, 0},
-    {"gemm_big_mfma", 16, 1}, {"head_down_split", 0, 1}, {"dec_gpw_qkv", 1, 1}, {"dec_gpw_res", 1, 1}, {"dec_gpw_mlp", 3, 1}, {"dec_gpw_down", 2, 1}, {"dec_gpw_out", 3, 1}, {"dec_gpw_hmlp", 11, 1},
+    {"dec_gpw_qkv", 1, 0}, {"dec_gpw_res", 1, 0}, {"dec_gpw_mlp", 3, 0}, {"dec_gpw_down", 2, 0}, {"dec_gpw_out", 3, 0}, {"dec_gpw_hmlp", 11, 0},
+    {"gemm_big_mfma", 16, 1}, {"head_down_split", 0, 1},
     {"attn_lab", 0, 1}, {"attn_nw", 4, 1},
 };
 static std::atomic<long long> g_opt_val[OPT_COUNT];
@@ -116,6 +117,7 @@ int hvx_set_option(const char* key, int64_t value) {
     if (i == OPT_GEMM_BIG_MFMA && value != 16 && value != 32) return set_error("hvx_set_option: gemm_big_mfma must be 16 or 32, got %lld", (long long)value), -1;
     if (i == OPT_DEC_FUSE_ROWS && (value < 0 || value > 256)) return set_error("hvx_set_option: dec_fuse_rows must be 0..256, got %lld", (long long)value), -1;
     if ((i == OPT_X3P8 || i == OPT_CONV_RESIDENT || i == OPT_CONV64_RESIDENT) && value != 0 && value != 1) return set_error("hvx_set_option: %s must be 0 or 1, got %lld", key, (long long)value), -1;
+    if (i >= OPT_DEC_GPW_QKV && i <= OPT_DEC_GPW_HMLP && (value < 1 || value > 64)) return set_error("hvx_set_option: %s must be 1..64, got %lld", key, (long long)value), -1;
     if (i == OPT_ATT_WAVES && value != 4 && value != 8) return set_error("hvx_set_option: att_waves must be 4 or 8, got %lld", (long long)value), -1;
     #ifdef HVX_LAB
     const bool form_ok = value == 0 || value == 16 || value == 17 || value == 32 || value == 48;
@@ -291,6 +293,49 @@ int hvx_op_skinny_gemm(int32_t dtype, int32_t M, int32_t N, int32_t K, const voi
     memset(&r, 0, sizeof(r));
     r.x = out_f32; r.ldx = ldo; r.part = part_ws; r.split_k = split_k; r.part_stride = (long long)M * N; r.bias = bias;
     r.M = M; r.H = N; r.rows_per_z = M; r.dtype = DT_F32;
+    return launch_reduce_rmsnorm(r, (hipStream_t)s);
+}
+
+int hvx_op_decode_gemm(const hvx_decode_gemm_args* a, hvx_stream s) {
+    if (!a) return set_error("hvx_op_decode_gemm: null args"), -1;
+    if (a->form != 0 && a->form != 1) return set_error("hvx_op_decode_gemm: form %d: 0 (generic kernels) or 1 (wide-grid decode kernels)", a->form), -1;
+    if (a->dtype != DT_F32 && a->dtype != DT_BF16) return set_error("hvx_op_decode_gemm: dtype %d: fp32 (0) or bf16 (1) only", a->dtype), -1;
+    if (a->epi < SK_PARTIAL || a->epi > SK_RESID) return set_error("hvx_op_decode_gemm: bad epilogue %d", a->epi), -1;
+    if (!a->A || !a->W || a->M <= 0 || a->N <= 0 || a->K <= 0) return set_error("hvx_op_decode_gemm: null operand or empty shape"), -1;
+    // the generic kernels do not look at these fields: they would run, and compute something else
+    if (a->form == 0 && (a->a_frag || a->out_frag || a->w_fp8)) return set_error("hvx_op_decode_gemm: a_frag / out_frag / w_fp8 belong to form 1"), -1;
+    if (a->form == 1 && !a->a_frag) return set_error("hvx_op_decode_gemm: form 1 reads A in fragment order (a_frag = 1)"), -1;
+    SkinnyArgs k;
+    memset(&k, 0, sizeof(k));
+    k.dtype = a->dtype; k.M = a->M; k.N = a->N; k.K = a->K; k.A = a->A; k.lda = a->lda; k.W = a->W;
+    k.split_k = a->split_k < 1 ? 1 : a->split_k; k.epi = a->epi; k.bias = a->bias; k.part = a->part;
+    k.out = a->out; k.out_f32 = a->out_f32; k.ldo = a->ldo; k.out2 = a->out2; k.ldo2 = a->ldo2;
+    k.kn = a->kn; k.q_heads = a->q_heads; k.kv_heads = a->kv_heads; k.slot = a->slot; k.pos0 = a->pos0; k.n_new = a->n_new;
+    k.rope_cos = a->rope_cos; k.rope_sin = a->rope_sin; k.qbuf = a->qbuf; k.kcache = a->kcache; k.vTcache = a->vTcache;
+    k.max_ctx = a->max_ctx; k.kv_frag = a->kv_frag;
+    k.nz = a->nz < 1 ? 1 : a->nz; k.w_zs = a->w_zs; k.a_zs = a->a_zs; k.bias_zs = a->bias_zs; k.out_zs = a->out_zs; k.part_zs = a->part_zs;
+    k.n_valid = a->n_valid; k.a_norm = a->a_norm; k.norm_eps = a->norm_eps;
+    k.a_frag = a->a_frag; k.out_frag = a->out_frag;
+    k.w_fp8 = a->w_fp8; k.w_scale = a->w_scale; k.w_scale_zs = a->w_scale_zs;
+    if (a->form == 0) return launch_skinny(k, (hipStream_t)s);
+    const int rc = launch_dec_gemm(k, (hipStream_t)s);
+    if (rc == 1) return 0;
+    if (rc == 0)
+        return set_error("hvx_op_decode_gemm: form 1 does not take this launch (dtype %d, epi %d, M %d, N %d, K %d, split_k %d, nz %d, option dec_gemm %d)",
+                         k.dtype, k.epi, k.M, k.N, k.K, k.split_k, k.nz, (int)opt(OPT_DEC_GEMM)), -1;
+    return -1;
+}
+
+int hvx_op_reduce_rmsnorm(const hvx_reduce_rmsnorm_args* a, hvx_stream s) {
+    if (!a || !a->x) return set_error("hvx_op_reduce_rmsnorm: null argument"), -1;
+    if (a->dtype != DT_F32 && a->dtype != DT_BF16) return set_error("hvx_op_reduce_rmsnorm: dtype %d: fp32 (0) or bf16 (1) only", a->dtype), -1;
+    if (a->M <= 0 || a->H <= 0) return set_error("hvx_op_reduce_rmsnorm: empty shape"), -1;
+    ReduceNormArgs r;
+    memset(&r, 0, sizeof(r));
+    r.x = a->x; r.ldx = a->ldx; r.part = a->part; r.split_k = a->split_k; r.part_stride = a->part_stride; r.part_zs = a->part_zs;
+    r.bias = a->bias; r.bias_zs = a->bias_zs; r.gain = a->gain; r.gain_zs = a->gain_zs; r.eps = a->eps; r.do_norm = a->do_norm;
+    r.y = a->y; r.ldy = a->ldy; r.dtype = a->dtype; r.M = a->M; r.H = a->H; r.rows_per_z = a->rows_per_z;
+    r.y_frag = a->y_frag; r.y_frag_zrows = a->y_frag_zrows;
     return launch_reduce_rmsnorm(r, (hipStream_t)s);
 }
 

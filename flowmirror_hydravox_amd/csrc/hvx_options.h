@@ -1,6 +1,6 @@
 // hvx_options.h — the library's run-time options: ONE mechanism, visible to the C-ABI caller (hvx_set_option / hvx_get_option / hvx_option_name in
 // include/hvx.h), instead of environment variables read through function-local statics.  None of them changes a result's CONTRACT: they pick between forms
-// the parity tests hold to each other (dec_gemm: tests/test_gpu_fullsize.py; conv64_resident, x3p8: tests/test_gpu_planes.py, operator by operator) or tune a launch geometry.  Numerics that a caller may care about are NOT here:
+// the parity tests hold to each other (dec_gemm: tests/test_gpu_fullsize.py at model level, tests/test_gpu_decode_gemm.py for the bound of each GEMM against float64; conv64_resident, x3p8: tests/test_gpu_planes.py, operator by operator) or tune a launch geometry.  Numerics that a caller may care about are NOT here:
 // the vocoder's exact-fp32 form is a field of hvx_hift_config / hvx_hifigan_config.  Options marked `lab` exist for timing studies (tools/): the shipped
 // library refuses to set them — they are settable only in a library compiled with -DHVX_LAB (python -m flowmirror_hydravox_amd.build --lab ...).
 // Values are read at dispatch time (an atomic load per launch decision); a captured step graph keeps the forms it was captured with.
@@ -27,10 +27,13 @@ enum OptId : int {
                                // 16 = the in-tile pipeline everywhere (the round-5 tile), 32 = the 32x32x16 tile (measured slower, kept selectable)
     OPT_DEC_FUSE_ROWS,         // decode grids of up to this many rows build the o_proj's activation fragments from the attention's key-split partials (no combine launch);
                                // 0 = never (the default: bit-identical and measured 12 % SLOWER per step, profiles/r06_decode_fuse_ab.log — kept selectable for that A / B)
+    // column groups per workgroup of the decode GEMM launches (gemm_dec.hip), 1..64; the defaults are the tuned values.  A launch geometry only: every
+    // value computes the same sums in the same order.  Settable in the shipped library because tests/test_gpu_decode_gemm.py moves the grid's edges with
+    // them (a tail workgroup with fewer groups than the others, workgroups that return at once), operator by operator against float64.
+    OPT_DEC_GPW_QKV, OPT_DEC_GPW_RES, OPT_DEC_GPW_MLP, OPT_DEC_GPW_DOWN, OPT_DEC_GPW_OUT, OPT_DEC_GPW_HMLP,
     // ---- lab (settable with -DHVX_LAB only) ----
     OPT_GEMM_BIG_MFMA,         // MFMA shape of the 256-tile Linear's K-loop: 16 (16x16x32) or 32 (32x32x16: bit-identical, measured 4 % slower)
     OPT_HEAD_DOWN_SPLIT,       // forced K split of the MTP heads' down projection; 0 = chosen per grid
-    OPT_DEC_GPW_QKV, OPT_DEC_GPW_RES, OPT_DEC_GPW_MLP, OPT_DEC_GPW_DOWN, OPT_DEC_GPW_OUT, OPT_DEC_GPW_HMLP,   // column groups per workgroup of the decode GEMM launches
     OPT_ATTN_LAB,              // timing-only variants of the DiT attention loop (results are garbage): bit mask, see attention.hip
     OPT_ATTN_NW,               // 8: one 8-wave workgroup per CU for the DiT attention (lab)
     OPT_COUNT

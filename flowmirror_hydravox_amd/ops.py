@@ -6,7 +6,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import GemmArgs, AttnArgs, SampleArgs, ptr, stream_ptr, check, dtype_code
+from ._lib import GemmArgs, AttnArgs, SampleArgs, DecodeGemmArgs, ReduceNormArgs, ptr, stream_ptr, check, dtype_code
 
 
 def _pad32(n):
@@ -127,6 +127,49 @@ def skinny_gemm(x, w_packed, n_out, bias=None, split_k=1):
     check(lib.hvx_op_skinny_gemm(dtype_code(x.dtype), M, n_out, K, ptr(x), K, ptr(w_packed), ptr(bias), split_k, ptr(part), ptr(out),
                                  n_out, stream_ptr()), 'hvx_op_skinny_gemm')
     return out
+
+
+def decode_gemm(form, epi, M, N, K, A, W, *, lda=0, split_k=1, bias=None, part=None, out=None, ldo=0, out2=None, ldo2=0,
+                kn=0, q_heads=0, kv_heads=0, slot=None, pos0=None, n_new=None, rope_cos=None, rope_sin=None, qbuf=None, kcache=None, vTcache=None,
+                max_ctx=0, kv_frag=False, nz=1, w_zs=0, a_zs=0, bias_zs=0, out_zs=0, part_zs=0, n_valid=0, a_norm=False, norm_eps=0.0,
+                out_frag=False, w_scale=None, w_scale_zs=0):
+    """One GEMM of the AR decode step, out = A @ W^T through epilogue `epi` (_lib.SK_*), on the kernels `form` names: 0 = the generic kernels
+    (csrc/gemm_skinny.hip; A row-major [M][lda]), 1 = the wide-grid kernels (csrc/gemm_dec.hip; A = packing.frag_rows of the rows).  The arguments
+    are the fields of csrc/hvx_kernels.h: SkinnyArgs; buffers are the caller's, results land in them.  W: packing.pack_frag of [N][K], or uint8
+    packing.pack_frag_fp8 codes with `w_scale` (form 1, SwiGLU).  A shape form 1 does not instantiate raises HvxError: nothing falls through to
+    the other kernels."""
+    lib = _lib.load()
+    a = DecodeGemmArgs()
+    a.form, a.dtype, a.M, a.N, a.K = int(form), dtype_code(A.dtype), M, N, K
+    a.A, a.lda, a.W, a.split_k, a.epi, a.bias, a.part = ptr(A), lda, ptr(W), split_k, int(epi), ptr(bias), ptr(part)
+    if out is not None:
+        a.out, a.out_f32, a.ldo = ptr(out), int(out.dtype == torch.float32), ldo
+    a.out2, a.ldo2 = ptr(out2), ldo2
+    a.kn, a.q_heads, a.kv_heads, a.slot, a.pos0, a.n_new = kn, q_heads, kv_heads, ptr(slot), ptr(pos0), ptr(n_new)
+    for t in (slot, pos0, n_new):
+        assert t is None or t.dtype == torch.int32
+    a.rope_cos, a.rope_sin, a.qbuf, a.kcache, a.vTcache = ptr(rope_cos), ptr(rope_sin), ptr(qbuf), ptr(kcache), ptr(vTcache)
+    a.max_ctx, a.kv_frag = max_ctx, int(kv_frag)
+    a.nz, a.w_zs, a.a_zs, a.bias_zs, a.out_zs, a.part_zs = nz, w_zs, a_zs, bias_zs, out_zs, part_zs
+    a.n_valid, a.a_norm, a.norm_eps = n_valid, int(a_norm), norm_eps
+    a.a_frag, a.out_frag = int(form == 1), int(out_frag)
+    if W.dtype == torch.uint8:
+        a.w_fp8, a.w_scale, a.w_scale_zs = 1, ptr(w_scale), w_scale_zs
+    check(lib.hvx_op_decode_gemm(C.byref(a), stream_ptr()), 'hvx_op_decode_gemm')
+
+
+def reduce_rmsnorm(x, *, M, H, ldx, part=None, split_k=0, part_stride=0, part_zs=0, bias=None, bias_zs=0, gain=None, gain_zs=0, eps=0.0, do_norm=False,
+                   y=None, ldy=0, rows_per_z=0, y_frag=False, y_frag_zrows=0):
+    """x[m, :] += sum_s part[s][m][:] (+ bias) in place on the fp32 rows x; y[m, :] = dtype(rmsnorm(x[m, :]) * gain), or dtype(x[m, :]) without do_norm
+    (csrc/hvx_kernels.h: ReduceNormArgs).  y_frag: the 16-bit y leaves in fragment order (packing.frag_rows)."""
+    lib = _lib.load()
+    assert x.dtype == torch.float32
+    a = ReduceNormArgs()
+    a.x, a.ldx, a.part, a.split_k, a.part_stride, a.part_zs = ptr(x), ldx, ptr(part), split_k, part_stride, part_zs
+    a.bias, a.bias_zs, a.gain, a.gain_zs, a.eps, a.do_norm = ptr(bias), bias_zs, ptr(gain), gain_zs, eps, int(do_norm)
+    a.y, a.ldy, a.dtype = ptr(y), ldy, dtype_code(y.dtype) if y is not None else _lib.F32
+    a.M, a.H, a.rows_per_z, a.y_frag, a.y_frag_zrows = M, H, rows_per_z, int(y_frag), y_frag_zrows
+    check(lib.hvx_op_reduce_rmsnorm(C.byref(a), stream_ptr()), 'hvx_op_reduce_rmsnorm')
 
 
 def ras_sample(logp, hist, hist_len, min_len, noise, cursor, *, speech_tokens, top_k, top_p, win_size, rep_thresh, active=None,

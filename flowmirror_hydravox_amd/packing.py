@@ -2,6 +2,8 @@
 
 * `pack_frag`      — [N][K] row-major -> MFMA fragment order [N/16][K/32][64 lanes][8] consumed by the decode GEMMs
                       (csrc/gemm_skinny.hip): lane l = g*16 + r holds row r of the 16-row tile, k = 8g..8g+7.
+* `frag_rows`, `kfrag`, `vfrag` (+ inverses) — the same fragment order for activation rows and the LLM's KV cache
+                      (csrc/hvx_device.h: frag_index, vfrag_index): how the tests build and decode what csrc/gemm_dec.hip reads and writes.
 * `conv_weight`    — torch Conv1d weight [Cout][Cin][k] -> [Cout][k][Cin_pad32] (k-major so that a tap is a row shift
                       of the time-major activation; csrc/gemm_tiled.hip).
 * `fold_weight_norm` — w = v * (g / ||v||), the new-style parametrisation of hifigan/generator.py:26-29.
@@ -25,6 +27,50 @@ def pack_frag(w):
     w = pad_to(w, 0, 16)
     N, K = w.shape
     return w.view(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(N, K)
+
+
+def frag_rows(x):
+    """[rows][K] activations -> flat fragment order [ceil(rows/16)][K/32][g=4][r=16][8] (csrc/hvx_device.h: frag_index(row, k, K / 32)): what the
+    wide-grid decode GEMMs read as their A operand (csrc/gemm_dec.hip).  Rows are zero-padded to a multiple of 16; the same permutation as pack_frag."""
+    return pack_frag(x).reshape(-1)
+
+
+def unfrag_rows(f, rows, K):
+    """inverse of frag_rows: flat fragment-order tensor (at least ceil(rows/16)*16*K elements) -> [rows][K]"""
+    assert K % 32 == 0
+    R = (rows + 15) // 16 * 16
+    return f.reshape(-1)[:R * K].view(R // 16, K // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(R, K)[:rows]
+
+
+def kfrag(k):
+    """[..., ctx, 64] keys -> the fragment-order K cache of a (slot, kv head) block, [..., ctx * 64] (ctx % 16 == 0): frag_index(pos, d, 2) of
+    csrc/hvx_device.h, i.e. frag_rows with two k-steps per row"""
+    ctx = k.shape[-2]
+    assert k.shape[-1] == 64 and ctx % 16 == 0, k.shape
+    lead = k.shape[:-2]
+    return k.reshape(*lead, ctx // 16, 16, 2, 4, 8).permute(*range(len(lead)), -5, -3, -2, -4, -1).reshape(*lead, ctx * 64)
+
+
+def unkfrag(f, ctx):
+    """inverse of kfrag: [..., ctx * 64] -> [..., ctx, 64]"""
+    lead = f.shape[:-1]
+    return f.reshape(*lead, ctx // 16, 2, 4, 16, 8).permute(*range(len(lead)), -5, -2, -4, -3, -1).reshape(*lead, ctx, 64)
+
+
+def vfrag(vT):
+    """[..., 64, ctx] transposed values -> the fragment-order V cache of a (slot, kv head) block, [..., ctx * 64] (ctx % 32 == 0): vfrag_index(pos, d)
+    of csrc/hvx_device.h — per 32-key block four d-tiles of [64 lanes][8], lane (d & 15) + 16 g holding keys {4g..4g+3, 16+4g..16+4g+3} of the block"""
+    ctx = vT.shape[-1]
+    assert vT.shape[-2] == 64 and ctx % 32 == 0, vT.shape
+    lead = vT.shape[:-2]
+    # d = (dt, dl); pos = (blk, half, g, e) with pos & 31 = 16 half + 4 g + e  ->  [blk][dt][g][dl][half][e]
+    return vT.reshape(*lead, 4, 16, ctx // 32, 2, 4, 4).permute(*range(len(lead)), -4, -6, -2, -5, -3, -1).reshape(*lead, ctx * 64)
+
+
+def unvfrag(f, ctx):
+    """inverse of vfrag: [..., ctx * 64] -> [..., 64, ctx]"""
+    lead = f.shape[:-1]
+    return f.reshape(*lead, ctx // 32, 4, 4, 16, 2, 4).permute(*range(len(lead)), -5, -3, -6, -2, -4, -1).reshape(*lead, 64, ctx)
 
 
 def pack_narrow4(w):

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define HVX_ABI_VERSION 5
+#define HVX_ABI_VERSION 6
 #define HVX_F32 0
 #define HVX_BF16 1
 #define HVX_F16 2                         /* IEEE fp16: hvx_flow_config.dtype only (the flow's fp16 mode) */
@@ -135,6 +135,49 @@ int hvx_op_resample_linear(const float* x, int32_t rows, int32_t t_in, float* y,
 /* packs a row-major [N][K] weight into the MFMA fragment order used by the decode GEMMs: [N/16][K/32][64][8] */
 int hvx_op_skinny_gemm(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* Wpacked,
                        const float* bias, int32_t split_k, float* part_ws, float* out_f32, int32_t ldo, hvx_stream s);
+
+/* One GEMM of the AR decode step with any of its five epilogues (csrc/hvx_kernels.h: SkinnyArgs / SkinnyEpi, field for field; epi 0 = split-K partials,
+ * 1 = store, 2 = QKV + RoPE + KV-cache scatter, 3 = SwiGLU, 4 = in-place residual update), on the kernels `form` names:
+ *   form 0: the generic kernels of gemm_skinny.hip, A row-major [M][lda];
+ *   form 1: the wide-grid A-stationary / weight-ring kernels of gemm_dec.hip, A in fragment order (a_frag = 1).  A shape that form does not
+ *           instantiate is an ERROR here (the model falls back to form 0; a test must know which kernel it ran).
+ * W is packing.pack_frag([N][K]) (w_fp8: packing.pack_frag_fp8 codes + w_scale per column).  The narrow weight layout and the fused attention
+ * combine of SkinnyArgs are not reachable through this entry. */
+typedef struct {
+    int32_t form;
+    int32_t dtype, M, N, K;
+    const void* A; int32_t lda;
+    const void* W;
+    int32_t split_k, epi;
+    const float* bias;
+    float* part;                                   /* [split_k][M][N] */
+    void* out; int32_t out_f32, ldo;
+    void* out2; int32_t ldo2;
+    int32_t kn, q_heads, kv_heads;
+    const int32_t* slot; const int32_t* pos0; const int32_t* n_new;
+    const float* rope_cos; const float* rope_sin;
+    void* qbuf; void* kcache; void* vTcache;
+    int32_t max_ctx, kv_frag;
+    int32_t nz; int64_t w_zs, a_zs, bias_zs, out_zs, part_zs;
+    int32_t n_valid;
+    int32_t a_norm; float norm_eps;
+    int32_t a_frag, out_frag;
+    int32_t w_fp8; const float* w_scale; int64_t w_scale_zs;
+} hvx_decode_gemm_args;
+int hvx_op_decode_gemm(const hvx_decode_gemm_args* a, hvx_stream s);
+
+/* x[m,:] += sum_s part[s][m][:] (+ bias);  y[m,:] = dtype(rmsnorm(x[m,:]) * gain)  (do_norm 0: y = dtype(x)) — the split-K reduce of the decode
+ * step (csrc/hvx_kernels.h: ReduceNormArgs, field for field).  y_frag: y (16-bit) leaves in fragment order, the A operand of a form-1 GEMM. */
+typedef struct {
+    float* x; int32_t ldx;
+    const float* part; int32_t split_k; int64_t part_stride, part_zs;
+    const float* bias; int64_t bias_zs;
+    const float* gain; int64_t gain_zs; float eps; int32_t do_norm;
+    void* y; int32_t ldy, dtype;
+    int32_t M, H, rows_per_z;
+    int32_t y_frag, y_frag_zrows;
+} hvx_reduce_rmsnorm_args;
+int hvx_op_reduce_rmsnorm(const hvx_reduce_rmsnorm_args* a, hvx_stream s);
 
 /* ---------------------------------------------------------------------------------------------------
  * LLM — replaces CosyVoice3LM.inference_wrapper's per-step math (cosyvoice/llm/llm_multi_head_v3.py

@@ -192,7 +192,8 @@ def test_wide_grid_decode_gemm_form_agrees_with_the_generic_kernels(S, K):
     too from 33 sequences on — gate / up with every head's rows as its own fragment-order matrix (40 sequences: padded to 48 rows per head), the
     shared output projection over the stacked rows of all heads (from 33 ROWS on: 20 sequences x 2 heads already).  The two differ in the fp32
     summation order of every GEMM (K is not split inside a workgroup any more) and in where bf16 roundings fall after it: log-probs of the
-    sampler's candidates within 3e-2 (measured 1.2e-2), appended K / V rows within 2e-2."""
+    sampler's candidates within 3e-2 (measured 1.2e-2), appended K / V rows within 2e-2.  These thresholds see two forms agree through two layers, a
+    softmax and a top-25 filter; the bound of each GEMM on its own, against a float64 product, is tests/test_gpu_decode_gemm.py."""
     import os
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))

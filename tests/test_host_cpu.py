@@ -39,7 +39,7 @@ def test_library_builds_and_exports_every_declared_symbol():
         assert hasattr(lib, name), 'libhvx.so does not export %s' % name
     # the ctypes binding covers exactly the header
     assert sorted(_lib.SYMBOLS.keys()) == declared
-    assert _lib.load().hvx_abi_version() == _lib.HVX_ABI_VERSION == 5
+    assert _lib.load().hvx_abi_version() == _lib.HVX_ABI_VERSION == 6
 
 
 def test_libhvx_holds_no_packed_fp32_instruction(tmp_path):
@@ -68,12 +68,14 @@ def test_ctypes_struct_sizes_match_the_c_header(tmp_path):
     """sizeof() of every argument struct as seen by a C compiler == the ctypes mirror (catches field drift)."""
     from flowmirror_hydravox_amd import _lib
     c = tmp_path / 's.c'
-    c.write_text('#include <stdio.h>\n#include "hvx.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(hvx_sample_args), '
-                 'sizeof(hvx_gemm_args), sizeof(hvx_attn_args), sizeof(hvx_llm_config), sizeof(hvx_flow_config), sizeof(hvx_hift_config), sizeof(hvx_decode_args), sizeof(hvx_nd));return 0;}\n')
+    c.write_text('#include <stdio.h>\n#include "hvx.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(hvx_sample_args), '
+                 'sizeof(hvx_gemm_args), sizeof(hvx_attn_args), sizeof(hvx_llm_config), sizeof(hvx_flow_config), sizeof(hvx_hift_config), sizeof(hvx_decode_args), sizeof(hvx_nd), '
+                 'sizeof(hvx_decode_gemm_args), sizeof(hvx_reduce_rmsnorm_args));return 0;}\n')
     exe = tmp_path / 's'
     subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(c), '-o', str(exe)])
     got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = [ctypes.sizeof(t) for t in (_lib.SampleArgs, _lib.GemmArgs, _lib.AttnArgs, _lib.LLMConfig, _lib.FlowConfig, _lib.HiftConfig, _lib.DecodeArgs, _lib.NdDesc)]
+    want = [ctypes.sizeof(t) for t in (_lib.SampleArgs, _lib.GemmArgs, _lib.AttnArgs, _lib.LLMConfig, _lib.FlowConfig, _lib.HiftConfig, _lib.DecodeArgs, _lib.NdDesc,
+                                            _lib.DecodeGemmArgs, _lib.ReduceNormArgs)]
     assert got == want
 
 
@@ -923,8 +925,12 @@ def test_library_options_are_one_switchboard_and_lab_ones_are_refused():
     with _lib.option_scope(attn_dit_form=16, dec_fuse_rows=16):           # the round-5 attention tile / the fused narrow-grid o_proj stay selectable for A / B runs
         assert _lib.get_option('attn_dit_form') == 16 and _lib.get_option('dec_fuse_rows') == 16
     assert _lib.get_option('attn_dit_form') == 0 and _lib.get_option('dec_fuse_rows') == 0
+    assert not opts['dec_gpw_qkv'][2]
+    with _lib.option_scope(dec_gpw_qkv=3, dec_gpw_hmlp=2):                # the decode GEMMs' launch geometry: tests/test_gpu_decode_gemm.py moves the grid's edges with it
+        assert _lib.get_option('dec_gpw_qkv') == 3 and _lib.get_option('dec_gpw_hmlp') == 2
+    assert _lib.get_option('dec_gpw_qkv') == 1 and _lib.get_option('dec_gpw_hmlp') == 11
     for key, val, msg in (('no_such_option', 1, 'unknown option'), ('att_chunk', 100, 'multiple of 128'), ('att_waves', 5, '4 or 8'), ('attn_lab', 3, 'lab option'),
-                          ('attn_dit_form', 18, '0, 16, 17 or 32'), ('attn_dit_form', 48, 'lab builds only'), ('dec_fuse_rows', 300, '0..256'),
+                          ('attn_dit_form', 18, '0, 16, 17 or 32'), ('attn_dit_form', 48, 'lab builds only'), ('dec_fuse_rows', 300, '0..256'), ('dec_gpw_qkv', 0, '1..64'), ('dec_gpw_down', 65, '1..64'),
                           ('x3p8', 2, 'x3p8 must be 0 or 1'), ('conv64_resident', -1, 'conv64_resident must be 0 or 1'), ('conv_resident', 8, 'conv_resident must be 0 or 1')):
         with pytest.raises(_lib.HvxError, match=msg):
             _lib.set_option(key, val)
@@ -932,6 +938,57 @@ def test_library_options_are_one_switchboard_and_lab_ones_are_refused():
     for f in os.listdir(csrc):
         if f.endswith(('.hip', '.h')):
             assert 'getenv' not in open(os.path.join(csrc, f)).read(), f
+
+
+def test_fragment_order_helpers_equal_the_index_formulas_element_by_element():
+    """packing.frag_rows / kfrag / vfrag and their inverses against csrc/hvx_device.h: frag_index / vfrag_index restated as plain per-element loops.
+    tests/test_gpu_decode_gemm.py builds the kernels' A operands and decodes their fragment-order outputs with these helpers, so that it does not
+    share the kernels' own addressing."""
+    from flowmirror_hydravox_amd import packing
+
+    def frag_index(row, k, KT):
+        return ((row >> 4) * KT + (k >> 5)) * 512 + (((row & 15) + ((k & 24) << 1)) << 3) + (k & 7)
+
+    def vfrag_index(pos, d):
+        kk = pos & 31
+        return (pos >> 5) * 2048 + ((d >> 4) << 9) + (((d & 15) + ((kk & 12) << 2)) << 3) + ((kk >> 4) << 2) + (kk & 3)
+
+    rows, K = 35, 96
+    x = torch.arange(1, rows * K + 1, dtype=torch.float32).view(rows, K)          # every element its own value
+    f = packing.frag_rows(x)
+    assert f.shape == (48 * K,)
+    want = torch.zeros(48 * K)
+    for r in range(rows):
+        for k in range(K):
+            want[frag_index(r, k, K // 32)] = x[r, k]
+    assert torch.equal(f, want)                                                   # (the padding rows are zeros in both)
+    assert torch.equal(packing.unfrag_rows(f, rows, K), x)
+    assert torch.equal(packing.frag_rows(x), packing.pack_frag(x).reshape(-1))    # activations and weights share ONE fragment order
+
+    ctx, npos = 96, 70
+    k = torch.zeros(2, 3, ctx, 64)
+    k[:, :, :npos] = torch.arange(1, 2 * 3 * npos * 64 + 1, dtype=torch.float32).view(2, 3, npos, 64)
+    kf = packing.kfrag(k)
+    assert kf.shape == (2, 3, ctx * 64)
+    vT = k.transpose(-1, -2).contiguous()
+    vf = packing.vfrag(vT)
+    assert vf.shape == (2, 3, ctx * 64)
+    want_k, want_v = torch.zeros(2, 3, ctx * 64), torch.zeros(2, 3, ctx * 64)
+    seen_k, seen_v = set(), set()
+    for pos in range(npos):
+        for d in range(64):
+            ik, iv = frag_index(pos, d, 2), vfrag_index(pos, d)
+            seen_k.add(ik)
+            seen_v.add(iv)
+            want_k[:, :, ik] = k[:, :, pos, d]
+            want_v[:, :, iv] = vT[:, :, d, pos]
+    assert len(seen_k) == len(seen_v) == npos * 64                                # both formulas are injective
+    assert torch.equal(kf, want_k) and torch.equal(vf, want_v)
+    assert torch.equal(packing.unkfrag(kf, ctx), k) and torch.equal(packing.unvfrag(vf, ctx), vT)
+    # the inverses also serve a single block (no leading dimensions) and any dtype
+    kb = k[1, 2].to(torch.bfloat16)
+    assert torch.equal(packing.unkfrag(packing.kfrag(kb), ctx), kb)
+    assert torch.equal(packing.unvfrag(packing.vfrag(kb.t().contiguous()), ctx), kb.t())
 
 
 def test_build_never_reuses_objects_of_other_flags(tmp_path):
