@@ -56,6 +56,20 @@ class AttnArgs(C.Structure):
                 ('n_splits', c_i32), ('split_chunk', c_i32), ('part_o', c_vp), ('part_ml', c_vp), ('chunk', c_i32), ('q_log2', c_i32)]
 
 
+class LlmAttnArgs(C.Structure):
+    _fields_ = [('dtype', c_i32), ('batch', c_i32), ('heads', c_i32), ('n_rows', c_i32), ('kn', c_i32),
+                ('q', c_vp), ('q_bs', c_i64), ('q_hs', c_i64), ('q_hi', c_i64), ('q_lo', c_i64),
+                ('k', c_vp), ('k_bs', c_i64), ('k_hs', c_i64),
+                ('vT', c_vp), ('v_bs', c_i64), ('v_hs', c_i64), ('v_ld', c_i32),
+                ('kv_slot', c_vp), ('kv_len', c_vp), ('kv_len_const', c_i32),
+                ('causal', c_i32), ('pos0', c_vp), ('n_valid_lo', c_vp),
+                ('chunk', c_i32), ('scale', c_f32), ('q_log2', c_i32),
+                ('out', c_vp), ('o_bs', c_i64), ('o_hs', c_i64), ('o_hi', c_i64), ('o_lo', c_i64),
+                ('n_splits', c_i32), ('split_chunk', c_i32), ('n_sub', c_i32), ('sub_chunk', c_i32),
+                ('part_o', c_vp), ('part_ml', c_vp), ('n_rows_pad', c_i32), ('skip_combine', c_i32),
+                ('kv_frag', c_i32), ('o_frag_kt', c_i32)]
+
+
 class DecodeGemmArgs(C.Structure):
     _fields_ = [('form', c_i32), ('dtype', c_i32), ('M', c_i32), ('N', c_i32), ('K', c_i32),
                 ('A', c_vp), ('lda', c_i32), ('W', c_vp), ('split_k', c_i32), ('epi', c_i32), ('bias', c_vp), ('part', c_vp),
@@ -65,7 +79,9 @@ class DecodeGemmArgs(C.Structure):
                 ('max_ctx', c_i32), ('kv_frag', c_i32),
                 ('nz', c_i32), ('w_zs', c_i64), ('a_zs', c_i64), ('bias_zs', c_i64), ('out_zs', c_i64), ('part_zs', c_i64),
                 ('n_valid', c_i32), ('a_norm', c_i32), ('norm_eps', c_f32), ('a_frag', c_i32), ('out_frag', c_i32),
-                ('w_fp8', c_i32), ('w_scale', c_vp), ('w_scale_zs', c_i64)]
+                ('w_fp8', c_i32), ('w_scale', c_vp), ('w_scale_zs', c_i64),
+                ('w_narrow', c_i32), ('att_o', c_vp), ('att_ml', c_vp), ('att_kvlen', c_vp),
+                ('att_splits', c_i32), ('att_chunk', c_i32), ('att_rows_pad', c_i32)]
 
 
 class ReduceNormArgs(C.Structure):
@@ -147,6 +163,7 @@ SYMBOLS = {
     'hvx_op_gemm': (c_i32, [C.POINTER(GemmArgs), c_vp]),
     'hvx_op_act_rows': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i64, c_i32, c_f32, c_vp, c_i64, c_i32, c_vp]),
     'hvx_op_attention': (c_i32, [C.POINTER(AttnArgs), c_vp]),
+    'hvx_op_llm_attention': (c_i32, [C.POINTER(LlmAttnArgs), c_vp]),
     'hvx_op_resample_linear': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp]),
     'hvx_op_skinny_gemm': (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
     'hvx_op_decode_gemm': (c_i32, [C.POINTER(DecodeGemmArgs), c_vp]),
@@ -213,8 +230,9 @@ SYMBOLS = {
 # SkinnyArgs / AttnArgs, fragment-order KV cache; 3: round 5; 4: round 6 — hvx_set_option / hvx_get_option / hvx_option_name / hvx_build_flags / hvx_is_lab_build,
 # `exact_fp32` in hvx_hift_config and hvx_hifigan_config; 5: the plane-pair / res2 / div fields of hvx_gemm_args and hvx_op_act_rows, for the parity tests of the
 # vocoder's plane-pair convolutions; 6: hvx_op_decode_gemm / hvx_op_reduce_rmsnorm, for the parity tests of the decode GEMMs, and the dec_gpw_* options settable
-# in the shipped library)
-HVX_ABI_VERSION = 6
+# in the shipped library; 7: hvx_op_llm_attention and the w_narrow / att_* fields of hvx_decode_gemm_args, for the parity tests of the LM layers' cache attention and
+# the narrow residual projection behind it)
+HVX_ABI_VERSION = 7
 
 _lib = None
 

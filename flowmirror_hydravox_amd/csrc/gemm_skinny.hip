@@ -802,7 +802,7 @@ int launch_skinny(const SkinnyArgs& a_in, hipStream_t s) {
     if (a.M <= 0) return 0;
     if (a.nz < 1) a.nz = 1;
     if (a.split_k < 1) a.split_k = 1;
-    if ((a.N & 15) || (a.K & 31) || (a.lda & 7)) {
+    if ((a.N & (a.w_narrow ? 3 : 15)) || (a.K & 31) || (a.lda & 7)) {                  // (the narrow form owns 4 output columns per workgroup, not a 16-column tile)
         set_error("launch_skinny: bad geometry M=%d N=%d K=%d lda=%d", a.M, a.N, a.K, a.lda);
         return -1;
     }

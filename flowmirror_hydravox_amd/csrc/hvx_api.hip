@@ -270,6 +270,27 @@ int hvx_op_attention(const hvx_attn_args* a, hvx_stream s) {
     return launch_attention(k, (hipStream_t)s);
 }
 
+int hvx_op_llm_attention(const hvx_llm_attn_args* a, hvx_stream s) {
+    if (!a) return set_error("hvx_op_llm_attention: null args"), -1;
+    if (a->dtype != DT_F32 && a->dtype != DT_BF16) return set_error("hvx_op_llm_attention: dtype %d: fp32 (0) or bf16 (1) only", a->dtype), -1;
+    if (!a->q || !a->k || !a->vT) return set_error("hvx_op_llm_attention: null q, k or vT"), -1;
+    if (!a->out && !(a->skip_combine && a->n_splits > 1)) return set_error("hvx_op_llm_attention: null out (only skip_combine with n_splits > 1 leaves it unwritten)"), -1;
+    AttnArgs k;
+    memset(&k, 0, sizeof(k));
+    k.dtype = a->dtype; k.batch = a->batch; k.heads = a->heads; k.n_rows = a->n_rows; k.kn = a->kn;
+    k.q = a->q; k.q_bs = a->q_bs; k.q_hs = a->q_hs; k.q_hi = a->q_hi; k.q_lo = a->q_lo;
+    k.k = a->k; k.k_bs = a->k_bs; k.k_hs = a->k_hs;
+    k.vT = a->vT; k.v_bs = a->v_bs; k.v_hs = a->v_hs; k.v_ld = a->v_ld;
+    k.kv_slot = a->kv_slot; k.kv_len = a->kv_len; k.kv_len_const = a->kv_len_const;
+    k.causal = a->causal; k.pos0 = a->pos0; k.n_valid_lo = a->n_valid_lo;
+    k.chunk = a->chunk; k.scale = a->scale; k.q_log2 = a->q_log2;
+    k.out = a->out; k.o_bs = a->o_bs; k.o_hs = a->o_hs; k.o_hi = a->o_hi; k.o_lo = a->o_lo;
+    k.n_splits = a->n_splits; k.split_chunk = a->split_chunk; k.n_sub = a->n_sub; k.sub_chunk = a->sub_chunk;
+    k.part_o = a->part_o; k.part_ml = a->part_ml; k.n_rows_pad = a->n_rows_pad; k.skip_combine = a->skip_combine;
+    k.kv_frag = a->kv_frag; k.o_frag_kt = a->o_frag_kt;
+    return launch_attention(k, (hipStream_t)s);
+}
+
 int hvx_op_resample_linear(const float* x, int32_t rows, int32_t t_in, float* y, int32_t t_out, hvx_stream s) {
     if (!x || !y) return set_error("hvx_op_resample_linear: null argument"), -1;
     return launch_resample_linear(x, rows, t_in, y, t_out, (hipStream_t)s);
@@ -301,10 +322,12 @@ int hvx_op_decode_gemm(const hvx_decode_gemm_args* a, hvx_stream s) {
     if (a->form != 0 && a->form != 1) return set_error("hvx_op_decode_gemm: form %d: 0 (generic kernels) or 1 (wide-grid decode kernels)", a->form), -1;
     if (a->dtype != DT_F32 && a->dtype != DT_BF16) return set_error("hvx_op_decode_gemm: dtype %d: fp32 (0) or bf16 (1) only", a->dtype), -1;
     if (a->epi < SK_PARTIAL || a->epi > SK_RESID) return set_error("hvx_op_decode_gemm: bad epilogue %d", a->epi), -1;
-    if (!a->A || !a->W || a->M <= 0 || a->N <= 0 || a->K <= 0) return set_error("hvx_op_decode_gemm: null operand or empty shape"), -1;
+    if ((!a->A && !a->att_o) || !a->W || a->M <= 0 || a->N <= 0 || a->K <= 0) return set_error("hvx_op_decode_gemm: null operand or empty shape"), -1;      // (the combining form does not read A)
     // the generic kernels do not look at these fields: they would run, and compute something else
     if (a->form == 0 && (a->a_frag || a->out_frag || a->w_fp8)) return set_error("hvx_op_decode_gemm: a_frag / out_frag / w_fp8 belong to form 1"), -1;
     if (a->form == 1 && !a->a_frag) return set_error("hvx_op_decode_gemm: form 1 reads A in fragment order (a_frag = 1)"), -1;
+    if (a->form == 1 && (a->w_narrow || a->att_o || a->att_ml || a->att_kvlen || a->att_splits || a->att_chunk || a->att_rows_pad))
+        return set_error("hvx_op_decode_gemm: w_narrow / att_* belong to form 0"), -1;
     SkinnyArgs k;
     memset(&k, 0, sizeof(k));
     k.dtype = a->dtype; k.M = a->M; k.N = a->N; k.K = a->K; k.A = a->A; k.lda = a->lda; k.W = a->W;
@@ -317,6 +340,8 @@ int hvx_op_decode_gemm(const hvx_decode_gemm_args* a, hvx_stream s) {
     k.n_valid = a->n_valid; k.a_norm = a->a_norm; k.norm_eps = a->norm_eps;
     k.a_frag = a->a_frag; k.out_frag = a->out_frag;
     k.w_fp8 = a->w_fp8; k.w_scale = a->w_scale; k.w_scale_zs = a->w_scale_zs;
+    k.w_narrow = a->w_narrow; k.att_o = a->att_o; k.att_ml = a->att_ml; k.att_kvlen = a->att_kvlen;
+    k.att_splits = a->att_splits; k.att_chunk = a->att_chunk; k.att_rows_pad = a->att_rows_pad;
     if (a->form == 0) return launch_skinny(k, (hipStream_t)s);
     const int rc = launch_dec_gemm(k, (hipStream_t)s);
     if (rc == 1) return 0;

@@ -6,7 +6,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import GemmArgs, AttnArgs, SampleArgs, DecodeGemmArgs, ReduceNormArgs, ptr, stream_ptr, check, dtype_code
+from ._lib import GemmArgs, AttnArgs, LlmAttnArgs, SampleArgs, DecodeGemmArgs, ReduceNormArgs, ptr, stream_ptr, check, dtype_code
 
 
 def _pad32(n):
@@ -132,15 +132,17 @@ def skinny_gemm(x, w_packed, n_out, bias=None, split_k=1):
 def decode_gemm(form, epi, M, N, K, A, W, *, lda=0, split_k=1, bias=None, part=None, out=None, ldo=0, out2=None, ldo2=0,
                 kn=0, q_heads=0, kv_heads=0, slot=None, pos0=None, n_new=None, rope_cos=None, rope_sin=None, qbuf=None, kcache=None, vTcache=None,
                 max_ctx=0, kv_frag=False, nz=1, w_zs=0, a_zs=0, bias_zs=0, out_zs=0, part_zs=0, n_valid=0, a_norm=False, norm_eps=0.0,
-                out_frag=False, w_scale=None, w_scale_zs=0):
+                out_frag=False, w_scale=None, w_scale_zs=0, w_narrow=False, att_o=None, att_ml=None, att_kvlen=None, att_splits=0, att_chunk=0, att_rows_pad=0):
     """One GEMM of the AR decode step, out = A @ W^T through epilogue `epi` (_lib.SK_*), on the kernels `form` names: 0 = the generic kernels
     (csrc/gemm_skinny.hip; A row-major [M][lda]), 1 = the wide-grid kernels (csrc/gemm_dec.hip; A = packing.frag_rows of the rows).  The arguments
     are the fields of csrc/hvx_kernels.h: SkinnyArgs; buffers are the caller's, results land in them.  W: packing.pack_frag of [N][K], or uint8
     packing.pack_frag_fp8 codes with `w_scale` (form 1, SwiGLU).  A shape form 1 does not instantiate raises HvxError: nothing falls through to
-    the other kernels."""
+    the other kernels.  Form 0, SK_RESID: w_narrow — W = packing.pack_narrow4 of [N][K] —, and with it att_o / att_ml (+ att_kvlen, att_splits, att_chunk,
+    att_rows_pad; kn, q_heads, kv_heads, pos0, n_new): A is then not read (it may be None when W tells the dtype) — its rows are combined from the partials an
+    ops.llm_attention(..., skip_combine=True) launch left."""
     lib = _lib.load()
     a = DecodeGemmArgs()
-    a.form, a.dtype, a.M, a.N, a.K = int(form), dtype_code(A.dtype), M, N, K
+    a.form, a.dtype, a.M, a.N, a.K = int(form), dtype_code((A if A is not None else W).dtype), M, N, K
     a.A, a.lda, a.W, a.split_k, a.epi, a.bias, a.part = ptr(A), lda, ptr(W), split_k, int(epi), ptr(bias), ptr(part)
     if out is not None:
         a.out, a.out_f32, a.ldo = ptr(out), int(out.dtype == torch.float32), ldo
@@ -155,7 +157,39 @@ def decode_gemm(form, epi, M, N, K, A, W, *, lda=0, split_k=1, bias=None, part=N
     a.a_frag, a.out_frag = int(form == 1), int(out_frag)
     if W.dtype == torch.uint8:
         a.w_fp8, a.w_scale, a.w_scale_zs = 1, ptr(w_scale), w_scale_zs
+    assert att_kvlen is None or att_kvlen.dtype == torch.int32
+    assert all(t is None or t.dtype == torch.float32 for t in (att_o, att_ml))
+    a.w_narrow, a.att_o, a.att_ml, a.att_kvlen = int(w_narrow), ptr(att_o), ptr(att_ml), ptr(att_kvlen)
+    a.att_splits, a.att_chunk, a.att_rows_pad = att_splits, att_chunk, att_rows_pad
     check(lib.hvx_op_decode_gemm(C.byref(a), stream_ptr()), 'hvx_op_decode_gemm')
+
+
+def llm_attention(q, k, vT, out, *, batch, heads, n_rows, kn, q_strides, k_strides, v_strides, v_ld, o_strides=(0, 0, 0, 0), kv_slot=None, kv_len=None,
+                  kv_len_const=0, causal=True, pos0=None, n_valid_lo=None, chunk=0, scale=0.125, q_log2=False, n_splits=1, split_chunk=0, n_sub=0, sub_chunk=0,
+                  part_o=None, part_ml=None, n_rows_pad=0, skip_combine=False, kv_frag=False, o_frag_kt=0):
+    """The LM layers' cache attention as hvx_llm_forward launches it (csrc/hvx_kernels.h: AttnArgs, field for field; csrc/attention.hip: attn_fwd_kernel,
+    attn_combine_kernel).  q_strides = (q_bs, q_hs, q_hi, q_lo), k_strides = (k_bs, k_hs), v_strides = (v_bs, v_hs), o_strides = (o_bs, o_hs, o_hi, o_lo), in
+    elements.  Buffers are the caller's, results land in them (`out`, or part_o / part_ml alone with skip_combine); nothing is defaulted beyond what
+    launch_attention itself applies."""
+    lib = _lib.load()
+    a = LlmAttnArgs()
+    given = [t for t in (q, k, vT, out) if t is not None]
+    assert given and all(t.dtype == given[0].dtype for t in given)
+    a.dtype, a.batch, a.heads, a.n_rows, a.kn = dtype_code(given[0].dtype), batch, heads, n_rows, kn
+    a.q, (a.q_bs, a.q_hs, a.q_hi, a.q_lo) = ptr(q), q_strides
+    a.k, (a.k_bs, a.k_hs) = ptr(k), k_strides
+    a.vT, (a.v_bs, a.v_hs), a.v_ld = ptr(vT), v_strides, v_ld
+    for t in (kv_slot, kv_len, pos0, n_valid_lo):
+        assert t is None or t.dtype == torch.int32
+    for t in (part_o, part_ml):
+        assert t is None or t.dtype == torch.float32
+    a.kv_slot, a.kv_len, a.kv_len_const, a.causal, a.pos0, a.n_valid_lo = ptr(kv_slot), ptr(kv_len), kv_len_const, int(causal), ptr(pos0), ptr(n_valid_lo)
+    a.chunk, a.scale, a.q_log2 = int(chunk), scale, int(q_log2)
+    a.out, (a.o_bs, a.o_hs, a.o_hi, a.o_lo) = ptr(out), o_strides
+    a.n_splits, a.split_chunk, a.n_sub, a.sub_chunk = n_splits, split_chunk, n_sub, sub_chunk
+    a.part_o, a.part_ml, a.n_rows_pad, a.skip_combine = ptr(part_o), ptr(part_ml), n_rows_pad, int(skip_combine)
+    a.kv_frag, a.o_frag_kt = int(kv_frag), o_frag_kt
+    check(lib.hvx_op_llm_attention(C.byref(a), stream_ptr()), 'hvx_op_llm_attention')
 
 
 def reduce_rmsnorm(x, *, M, H, ldx, part=None, split_k=0, part_stride=0, part_zs=0, bias=None, bias_zs=0, gain=None, gain_zs=0, eps=0.0, do_norm=False,

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define HVX_ABI_VERSION 6
+#define HVX_ABI_VERSION 7
 #define HVX_F32 0
 #define HVX_BF16 1
 #define HVX_F16 2                         /* IEEE fp16: hvx_flow_config.dtype only (the flow's fp16 mode) */
@@ -128,6 +128,26 @@ typedef struct {
 /* F.scaled_dot_product_attention (cosyvoice/flow/DiT/modules.py:391) */
 int hvx_op_attention(const hvx_attn_args* a, hvx_stream s);
 
+/* The cache attention of the LM layers in the form hvx_llm_forward launches it (csrc/hvx_kernels.h: AttnArgs, field for field; strides in elements): GQA-packed rows
+ * r = r_hi * kn + r_lo per (batch, kv head), causal over pos0[b] + r_lo, cache slot kv_slot[b], kv_len[b] keys, rows r_lo >= n_valid_lo[b] skipped, row-major or
+ * fragment-order (kv_frag) caches, key splits whose waves merge in LDS (sub_chunk), partials combined here or left to the consumer (skip_combine), row-major or
+ * fragment-order (o_frag_kt) output.  No defaults beyond launch_attention's own; `out` may be null only with skip_combine and n_splits > 1. */
+typedef struct {
+    int32_t dtype;                             /* HVX_F32 or HVX_BF16 */
+    int32_t batch, heads, n_rows, kn;
+    const void* q; int64_t q_bs, q_hs, q_hi, q_lo;
+    const void* k; int64_t k_bs, k_hs;
+    const void* vT; int64_t v_bs, v_hs; int32_t v_ld;
+    const int32_t* kv_slot; const int32_t* kv_len; int32_t kv_len_const;
+    int32_t causal; const int32_t* pos0; const int32_t* n_valid_lo;
+    int32_t chunk; float scale; int32_t q_log2;
+    void* out; int64_t o_bs, o_hs, o_hi, o_lo;
+    int32_t n_splits, split_chunk, n_sub, sub_chunk;
+    float* part_o; float* part_ml; int32_t n_rows_pad, skip_combine;
+    int32_t kv_frag, o_frag_kt;
+} hvx_llm_attn_args;
+int hvx_op_llm_attention(const hvx_llm_attn_args* a, hvx_stream s);
+
 /* F.interpolate(x, size=t_out, mode='linear') along the last axis of an f32 (rows, t_in) array: the `speed` knob of
  * inference_zero_shot / text_to_speech (infer_speech_model.py:583-588) and token2wav (cosyvoice/cli/model.py:424-426) */
 int hvx_op_resample_linear(const float* x, int32_t rows, int32_t t_in, float* y, int32_t t_out, hvx_stream s);
@@ -141,8 +161,10 @@ int hvx_op_skinny_gemm(int32_t dtype, int32_t M, int32_t N, int32_t K, const voi
  *   form 0: the generic kernels of gemm_skinny.hip, A row-major [M][lda];
  *   form 1: the wide-grid A-stationary / weight-ring kernels of gemm_dec.hip, A in fragment order (a_frag = 1).  A shape that form does not
  *           instantiate is an ERROR here (the model falls back to form 0; a test must know which kernel it ran).
- * W is packing.pack_frag([N][K]) (w_fp8: packing.pack_frag_fp8 codes + w_scale per column).  The narrow weight layout and the fused attention
- * combine of SkinnyArgs are not reachable through this entry. */
+ * W is packing.pack_frag([N][K]) (w_fp8: packing.pack_frag_fp8 codes + w_scale per column).  Form 0, epilogue 4 only: w_narrow — W is packing.pack_narrow4([N][K])
+ * for the 4-column workgroup form (K % 128 == 0, N % 4 == 0) — and with it att_o / att_ml / att_kvlen / att_splits / att_chunk / att_rows_pad: A is not read, its
+ * rows are combined from the key-split partials of an hvx_op_llm_attention launch with skip_combine (K = q_heads * 64 <= 1024; kn, q_heads, kv_heads, pos0, n_new
+ * as for that launch). */
 typedef struct {
     int32_t form;
     int32_t dtype, M, N, K;
@@ -163,6 +185,9 @@ typedef struct {
     int32_t a_norm; float norm_eps;
     int32_t a_frag, out_frag;
     int32_t w_fp8; const float* w_scale; int64_t w_scale_zs;
+    int32_t w_narrow;
+    const float* att_o; const float* att_ml; const int32_t* att_kvlen;
+    int32_t att_splits, att_chunk, att_rows_pad;
 } hvx_decode_gemm_args;
 int hvx_op_decode_gemm(const hvx_decode_gemm_args* a, hvx_stream s);
 

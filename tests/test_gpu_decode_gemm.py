@@ -265,6 +265,47 @@ def test_resid_updates_the_stream_in_place_and_copies_it(M, N):
 
 
 # ================================================================================================================================================
+# SK_RESID in the narrow weight layout (gemm_narrow_resid_kernel: the o_proj / down_proj of every decode grid of 32 rows or fewer)
+# ================================================================================================================================================
+@functools.lru_cache(maxsize=2)
+def _narrow_case(M, Kn, dtype):
+    N = 100
+    A, W = _randn((M, Kn), 1900 + M + Kn).to(dtype), _randn((N, Kn), 2000 + Kn, Kn ** -0.5).to(dtype)
+    bias, x0 = _randn((N,), 2100 + Kn, 0.5), _randn((M, N), 2200 + M + Kn, 2.0)
+    acc, mag = _prod(A, W)
+    return A, W, bias, x0, acc, mag
+
+
+@gpu
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32], ids=['bf16', 'fp32'])
+@pytest.mark.parametrize('Kn', [896, 4864, 5248])
+@pytest.mark.parametrize('M', [1, 7, 16, 17, 32])
+def test_narrow_resid_updates_the_stream_in_place_and_copies_it(M, Kn, dtype):
+    """x += A W^T + bias with W = packing.pack_narrow4 ([N/4][K/128][64][8]: a workgroup owns 4 output columns over the whole K, 8 waves share the 128-wide K blocks):
+    K = 896 (7 blocks: one per wave, wave 7 idle), 4864 (38 blocks: 5 per wave and request — 3 in fp32 —, a short last wave), 5248 (41 blocks: the K > 40 blocks form);
+    1 and 2 row tiles (blockIdx.z) with a clamped last row; N = 100 (25 workgroups) in strides of 104 / 108, the sentinel beyond N and beyond M; with and without
+    bias, with and without the copy in the operand type.  Bounds: the module docstring, fp32 outputs and the 16-bit copy of SK_RESID."""
+    A, W, bias, x0, acc, mag = _narrow_case(M, Kn, dtype)
+    N = W.shape[0]
+    ldo, ldo2 = N + 4, N + 8
+    Wd, Ad = _dev(packing.pack_narrow4(W)), _dev(A)
+    pad = lambda t, ld: torch.cat([torch.cat([t, torch.zeros(M, ld - N, dtype=t.dtype)], 1), torch.zeros(2, ld, dtype=t.dtype)])
+    for with_bias in (True, False):
+        ref = x0.double() + (acc + bias.double() if with_bias else acc)
+        e = _f32_bound(Kn, mag, ref)
+        for with_copy in (True, False):
+            x = _sent((M + 2) * ldo, torch.float32).view(M + 2, ldo)
+            x[:M, :N] = _dev(x0)
+            c = _sent((M + 2) * ldo2, dtype) if with_copy else None
+            ops.decode_gemm(0, SK_RESID, M, N, Kn, Ad, Wd, lda=Kn, bias=_dev(bias) if with_bias else None, out=x, ldo=ldo, out2=c, ldo2=ldo2, w_narrow=True)
+            torch.cuda.synchronize()
+            tag = 'narrow resid M=%d K=%d %s bias=%d copy=%d ' % (M, Kn, str(dtype)[6:], with_bias, with_copy)
+            _check(tag + 'stream', x, pad(ref, ldo), pad(e, ldo), pad(torch.ones(M, N), ldo) > 0)
+            if with_copy:
+                _check(tag + 'copy', c, pad(ref, ldo2), pad(_bf_bound(ref, e) if dtype == torch.bfloat16 else e, ldo2), pad(torch.ones(M, N), ldo2) > 0)
+
+
+# ================================================================================================================================================
 # SK_STORE: the stacked output projection
 # ================================================================================================================================================
 def _run_store(nz, S, N, n_valid, runs):

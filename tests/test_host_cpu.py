@@ -39,7 +39,7 @@ def test_library_builds_and_exports_every_declared_symbol():
         assert hasattr(lib, name), 'libhvx.so does not export %s' % name
     # the ctypes binding covers exactly the header
     assert sorted(_lib.SYMBOLS.keys()) == declared
-    assert _lib.load().hvx_abi_version() == _lib.HVX_ABI_VERSION == 6
+    assert _lib.load().hvx_abi_version() == _lib.HVX_ABI_VERSION == 7
 
 
 def test_libhvx_holds_no_packed_fp32_instruction(tmp_path):
@@ -68,14 +68,14 @@ def test_ctypes_struct_sizes_match_the_c_header(tmp_path):
     """sizeof() of every argument struct as seen by a C compiler == the ctypes mirror (catches field drift)."""
     from flowmirror_hydravox_amd import _lib
     c = tmp_path / 's.c'
-    c.write_text('#include <stdio.h>\n#include "hvx.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(hvx_sample_args), '
+    c.write_text('#include <stdio.h>\n#include "hvx.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(hvx_sample_args), '
                  'sizeof(hvx_gemm_args), sizeof(hvx_attn_args), sizeof(hvx_llm_config), sizeof(hvx_flow_config), sizeof(hvx_hift_config), sizeof(hvx_decode_args), sizeof(hvx_nd), '
-                 'sizeof(hvx_decode_gemm_args), sizeof(hvx_reduce_rmsnorm_args));return 0;}\n')
+                 'sizeof(hvx_decode_gemm_args), sizeof(hvx_reduce_rmsnorm_args), sizeof(hvx_llm_attn_args));return 0;}\n')
     exe = tmp_path / 's'
     subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(c), '-o', str(exe)])
     got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
     want = [ctypes.sizeof(t) for t in (_lib.SampleArgs, _lib.GemmArgs, _lib.AttnArgs, _lib.LLMConfig, _lib.FlowConfig, _lib.HiftConfig, _lib.DecodeArgs, _lib.NdDesc,
-                                            _lib.DecodeGemmArgs, _lib.ReduceNormArgs)]
+                                            _lib.DecodeGemmArgs, _lib.ReduceNormArgs, _lib.LlmAttnArgs)]
     assert got == want
 
 
@@ -989,6 +989,24 @@ def test_fragment_order_helpers_equal_the_index_formulas_element_by_element():
     kb = k[1, 2].to(torch.bfloat16)
     assert torch.equal(packing.unkfrag(packing.kfrag(kb), ctx), kb)
     assert torch.equal(packing.unvfrag(packing.vfrag(kb.t().contiguous()), ctx), kb.t())
+
+    # pack_narrow4 against the lane formula above csrc/gemm_skinny.hip: gemm_narrow_resid_kernel — workgroup nt, 128-wide K block kb, lane (c16, g) = c16 + 16 g holds
+    # W[4 nt + (c16 & 3)][128 kb + 32 (c16 >> 2) + 8 g .. + 8], at [nt][kb][lane][8] (the kernel's wp = W + (nt * KB + kb) * 512 + lane * 8)
+    N, K = 12, 384
+    w = torch.arange(1, N * K + 1, dtype=torch.float32).view(N, K)
+    p = packing.pack_narrow4(w).reshape(-1)
+    assert p.shape == (N * K,)
+    want, seen = torch.zeros(N * K), set()
+    for nt in range(N // 4):
+        for kb in range(K // 128):
+            for lane in range(64):
+                c16, g = lane & 15, lane >> 4
+                for e in range(8):
+                    i = (nt * (K // 128) + kb) * 512 + lane * 8 + e
+                    seen.add(i)
+                    want[i] = w[4 * nt + (c16 & 3), 128 * kb + 32 * (c16 >> 2) + 8 * g + e]
+    assert len(seen) == N * K and torch.equal(p, want)
+    assert torch.equal(packing.pack_narrow4(w.to(torch.bfloat16)).reshape(-1).float(), want.to(torch.bfloat16).float())
 
 
 def test_build_never_reuses_objects_of_other_flags(tmp_path):
