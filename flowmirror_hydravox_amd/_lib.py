@@ -165,6 +165,7 @@ SYMBOLS = {
     'hvx_op_attention': (c_i32, [C.POINTER(AttnArgs), c_vp]),
     'hvx_op_llm_attention': (c_i32, [C.POINTER(LlmAttnArgs), c_vp]),
     'hvx_op_resample_linear': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp]),
+    'hvx_op_resample_sinc': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i64, c_vp]),
     'hvx_op_skinny_gemm': (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
     'hvx_op_decode_gemm': (c_i32, [C.POINTER(DecodeGemmArgs), c_vp]),
     'hvx_op_reduce_rmsnorm': (c_i32, [C.POINTER(ReduceNormArgs), c_vp]),
@@ -231,7 +232,9 @@ SYMBOLS = {
 # `exact_fp32` in hvx_hift_config and hvx_hifigan_config; 5: the plane-pair / res2 / div fields of hvx_gemm_args and hvx_op_act_rows, for the parity tests of the
 # vocoder's plane-pair convolutions; 6: hvx_op_decode_gemm / hvx_op_reduce_rmsnorm, for the parity tests of the decode GEMMs, and the dec_gpw_* options settable
 # in the shipped library; 7: hvx_op_llm_attention and the w_narrow / att_* fields of hvx_decode_gemm_args, for the parity tests of the LM layers' cache attention and
-# the narrow residual projection behind it)
+# the narrow residual projection behind it).  The one exception to "bumped whenever a symbol is added": hvx_op_resample_sinc (the prompt resampler) joined at version
+# 7 — no struct changed and no existing symbol changed meaning, and a library of version 7 built before it fails in load() below on the missing symbol, with the
+# rebuild command, exactly as a version mismatch would.
 HVX_ABI_VERSION = 7
 
 _lib = None

@@ -296,6 +296,11 @@ int hvx_op_resample_linear(const float* x, int32_t rows, int32_t t_in, float* y,
     return launch_resample_linear(x, rows, t_in, y, t_out, (hipStream_t)s);
 }
 
+int hvx_op_resample_sinc(const float* x, int32_t rows, int32_t len, int64_t x_row_stride, const float* taps, int32_t orig, int32_t new_, int32_t width,
+                         float* y, int32_t out_len, int64_t y_row_stride, hvx_stream s) {
+    return launch_resample_sinc(x, rows, len, x_row_stride, taps, orig, new_, width, y, out_len, y_row_stride, (hipStream_t)s);      // (refuses what it cannot tile)
+}
+
 int hvx_op_skinny_gemm(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* Wpacked, const float* bias,
                        int32_t split_k, float* part_ws, float* out_f32, int32_t ldo, hvx_stream s) {
     if (dtype != DT_F32 && dtype != DT_BF16) return set_error("hvx_op_skinny_gemm: dtype %d: fp32 (0) or bf16 (1) only", dtype), -1;

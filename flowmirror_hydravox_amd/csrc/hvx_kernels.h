@@ -232,6 +232,9 @@ int launch_spectral_subtract(float* spec, int ld, int frames, int bins, const fl
 int launch_feature_post(float* x, int ld, int rows, int cols, int post, hipStream_t s);   // 1: whisper dynamic range + affine, 2: subtract column means
 int launch_overlap_add(const float* frames_buf, int ld, int frames, int n_fft, int hop, const float* wsq, float* y, int out_len, hipStream_t s);
 int launch_resample_linear(const float* x, int rows, int t_in, float* y, int t_out, hipStream_t s);   // F.interpolate(mode='linear') along the last axis
+// torchaudio.transforms.Resample (sinc_interp_hann) of `rows` waveforms (resample.hip): taps [2 * width + orig][nw] from packing.sinc_resample_taps, phase contiguous
+int launch_resample_sinc(const float* x, int rows, int len, long long x_rs, const float* taps, int orig, int nw, int width, float* y, int out_len, long long y_rs,
+                         hipStream_t s);
 int launch_transpose_f32(const float* src, float* dst, int rows, int cols, int ld_src, int ld_dst, hipStream_t s);   // dst[c][r] = src[r][c]
 int launch_rows_to_dtype(const float* src, int ld_src, void* dst, int dst_dtype, int ld_dst, int rows, int cols, int cols_pad, hipStream_t s);
 

@@ -7,14 +7,19 @@ the feature extraction — runs here as two GEMMs (framing x folded DFT basis, p
 The log-mel spectrogram the zero-shot frontend computes for the prompt audio — `feat_extractor` = matcha.utils.audio.mel_spectrogram (matcha/utils/audio.py:45-82, called at cosyvoice/cli/frontend.py:119;
 CosyVoice3 settings n_fft 1920, hop 480, win 1920, 80 mels, 24 kHz, fmin 0, fmax 8000).  Same call signature as the reference's partial:
     HvxMelSpectrogram(n_fft=1920, num_mels=80, sampling_rate=24000, hop_size=480, win_size=1920, fmin=0, fmax=8000)(y)  ->  (B, num_mels, frames)
-STFT and mel projection are fp32-MFMA GEMMs against bases built at construction (libhvx: hvx_mel_spectrogram); no CPU fallback."""
+STFT and mel projection are fp32-MFMA GEMMs against bases built at construction (libhvx: hvx_mel_spectrogram); no CPU fallback.
+
+In front of them: HvxResample, the band-limited resampler `load_wav` applies to a prompt of any sample rate (cosyvoice/utils/file_utils.py:46-75,
+torchaudio.transforms.Resample; libhvx: hvx_op_resample_sinc), and load_wav itself.  Around them: HvxFrontEnd, the reference's `frontend_zero_shot` /
+`frontend_sft` (cli/frontend.py:157-184) over these stages — what HvxModelManager's `frontend_factory` returns to serve raw prompts without torchaudio,
+whisper or onnxruntime.  The text tokenizer stays the caller's."""
 import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
 import ctypes as C
 
-from .packing import kaldi_fbank_bases, mel_filterbank, stft_bases, whisper_bases
+from .packing import kaldi_fbank_bases, mel_filterbank, sinc_resample_len, sinc_resample_taps, stft_bases, whisper_bases
 
 
 class HvxMelSpectrogram:
@@ -166,3 +171,150 @@ class HvxSpeakerEncoder:
         feat = self.feat(speech_16k.reshape(1, -1))                                         # [frames][80]
         out = self.runner.run({self.runner.g.inputs[0]: feat.unsqueeze(0)})[self.runner.g.outputs[0]]
         return torch.tensor([out.reshape(-1).tolist()], dtype=torch.float32, device=self.device)
+
+
+class HvxResample:
+    """`torchaudio.transforms.Resample(orig_freq, new_freq)` at its defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) on the device:
+    (L,) or (B, L) float -> (..., ceil(new * L / orig)).  The taps (packing.sinc_resample_taps) are built once and kept on the device; equal rates return
+    the input unchanged.  libhvx: hvx_op_resample_sinc (csrc/resample.hip), no CPU fallback."""
+
+    def __init__(self, orig_freq=16000, new_freq=16000, device='cuda'):
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.device = torch.device(device)
+        self._taps = None
+        if self.orig_freq != self.new_freq:
+            taps, self.width, self.orig, self.new = sinc_resample_taps(self.orig_freq, self.new_freq)      # (refuses a table over 64 MiB before any device work)
+            _lib.require_gpu()
+            self._taps = taps.t().contiguous().to(self.device)                                            # [K][new]: the phases of a tap contiguous
+
+    @torch.inference_mode()
+    def __call__(self, waveform):
+        if self._taps is None:
+            return waveform
+        from .ops import resample_sinc
+        x = waveform.to(self.device, torch.float32)
+        if x.dim() not in (1, 2):
+            raise ValueError('HvxResample takes (L,) or (B, L) waveforms, got %s' % (tuple(x.shape),))
+        rows = x.reshape(1, -1) if x.dim() == 1 else x
+        if rows.shape[1] > 1 and rows.stride(1) != 1:
+            rows = rows.contiguous()
+        if rows.numel() == 0:
+            y = rows.new_empty(rows.shape[0], sinc_resample_len(0, self.orig, self.new))
+        else:
+            y = resample_sinc(rows, self._taps, self.orig, self.new, self.width)
+        return y[0] if x.dim() == 1 else y
+
+
+_RESAMPLERS = {}
+
+
+def load_wav(wav, target_sr, min_sr=16000, device='cuda'):
+    """`load_wav` of the reference (cosyvoice/utils/file_utils.py:46-75) for audio that is already decoded: `wav` is (tensor | ndarray, sample_rate) with the
+    rate an int, float, numpy scalar or 0-d tensor, or a bare tensor / ndarray taken as already at `target_sr`; channels are averaged to mono, a rate below
+    `min_sr` fails the reference's assertion, and the resampling runs on the device (one HvxResample per (orig, new), kept) -> float32 (1, L) on `device`.
+    A file path raises NotImplementedError: there is no audio decoder here, the server hands over tensors."""
+    import numbers
+    import os
+    import numpy as np
+    sample_rate = None
+    if isinstance(wav, (tuple, list)) and len(wav) == 2:
+        wav, sample_rate = wav
+        if isinstance(sample_rate, torch.Tensor):
+            sample_rate = int(sample_rate.item())
+        elif isinstance(sample_rate, (np.generic, numbers.Real)):
+            sample_rate = int(sample_rate)
+    if isinstance(wav, torch.Tensor):
+        speech = wav.detach()
+    elif isinstance(wav, np.ndarray):
+        speech = torch.from_numpy(wav)
+    elif isinstance(wav, (str, bytes, os.PathLike)):
+        raise NotImplementedError('load_wav: %r is a file path; this package has no audio decoder — pass (tensor, sample_rate)' % (wav,))
+    else:
+        raise TypeError('load_wav: expected a tensor, an ndarray or (audio, sample_rate), got %s' % type(wav).__name__)
+    if speech.dim() == 1:
+        speech = speech.unsqueeze(0)
+    if not speech.is_floating_point():
+        raise TypeError('load_wav: %s audio; the reference decodes to float in [-1, 1]' % speech.dtype)
+    if speech.shape[0] > 1:
+        speech = speech.mean(dim=0, keepdim=True)
+    if sample_rate is None:
+        sample_rate = target_sr
+    if sample_rate != target_sr:
+        assert sample_rate >= min_sr, 'wav sample rate {} must be greater than {}'.format(sample_rate, target_sr)
+        key = (int(sample_rate), int(target_sr), str(device))
+        if key not in _RESAMPLERS:
+            _RESAMPLERS[key] = HvxResample(sample_rate, target_sr, device=device)
+        return _RESAMPLERS[key](speech)
+    return speech.to(device, torch.float32)
+
+
+class HvxFrontEnd:
+    """The zero-shot / speaker frontend of the reference (`CosyVoiceFrontEnd`, cosyvoice/cli/frontend.py:39-184) composed of this package's device stages,
+    for `HvxModelManager(frontend_factory=lambda args, cfg: HvxFrontEnd(...))`: raw prompt audio at any rate -> load_wav (HvxResample) -> HvxSpeechTokenizer,
+    HvxSpeakerEncoder and HvxMelSpectrogram, with the `feat = 2 x token` trim (:169-173).  The model inputs carry the reference's keys, dtypes and [1][N]
+    shapes (:157-184), on the device.
+      tokenize        text -> list[int]: the caller's text tokenizer (the reference's `get_tokenizer().encode`; out of scope here)
+      speech_tokenizer_onnx, campplus_onnx   the two ONNX assets (paths or onnx_graph.Graph), run by the device executor
+      spk2info        {spk_id: {'embedding': ...}} or the path of a torch-saved one ({} when absent, as the reference)
+      text_normalize  (text, split, text_frontend) -> list[str] | str; default: the reference's pass-through for text_frontend=False (no text normaliser here)
+    frontend_cross_lingual / frontend_instruct* / frontend_vc are not provided: the HydraVox server never calls them."""
+
+    def __init__(self, tokenize, speech_tokenizer_onnx, campplus_onnx, spk2info=None, text_normalize=None, allow_uncovered=False, device='cuda'):
+        import os
+        self.tokenize = tokenize
+        self.device = torch.device(device)
+        self.speech_tokenizer = HvxSpeechTokenizer(speech_tokenizer_onnx, device=device, allow_uncovered=allow_uncovered)
+        self.speaker_encoder = HvxSpeakerEncoder(campplus_onnx, device=device, allow_uncovered=allow_uncovered)
+        self.feat_extractor = HvxMelSpectrogram(device=device)                                # (the CosyVoice3 settings: 24 kHz, n_fft 1920, hop 480, 80 mels)
+        if isinstance(spk2info, (str, os.PathLike)):
+            spk2info = torch.load(spk2info, map_location=self.device) if os.path.exists(spk2info) else {}      # (:58-61)
+        self.spk2info = {} if spk2info is None else spk2info
+        self._text_normalize = text_normalize
+
+    def _extract_text_token(self, text):
+        tok = torch.tensor([list(self.tokenize(text))], dtype=torch.int32).reshape(1, -1).to(self.device)
+        return tok, torch.tensor([tok.shape[1]], dtype=torch.int32, device=self.device)
+
+    def _extract_speech_token(self, prompt_wav):
+        return self.speech_tokenizer(load_wav(prompt_wav, 16000, device=self.device))
+
+    def _extract_spk_embedding(self, prompt_wav):
+        return self.speaker_encoder(load_wav(prompt_wav, 16000, device=self.device))
+
+    def _extract_speech_feat(self, prompt_wav):
+        feat = self.feat_extractor(load_wav(prompt_wav, 24000, device=self.device)).transpose(1, 2).contiguous()      # [1][frames][80]
+        return feat, torch.tensor([feat.shape[1]], dtype=torch.int32, device=self.device)
+
+    def text_normalize(self, text, split=True, text_frontend=True):
+        if self._text_normalize is not None:
+            return self._text_normalize(text, split=split, text_frontend=text_frontend)
+        return [text] if split is True else text
+
+    def frontend_sft(self, tts_text, spk_id):
+        text, text_len = self._extract_text_token(tts_text)
+        embedding = self.spk2info[spk_id]['embedding']
+        return {'text': text, 'text_len': text_len, 'llm_embedding': embedding, 'flow_embedding': embedding}
+
+    def frontend_zero_shot(self, tts_text, prompt_text, prompt_wav, resample_rate, zero_shot_spk_id):
+        text, text_len = self._extract_text_token(tts_text)
+        if zero_shot_spk_id == '':
+            prompt_text_token, prompt_text_len = self._extract_text_token(prompt_text)
+            speech_feat, speech_feat_len = self._extract_speech_feat(prompt_wav)
+            wav_16k = (load_wav(prompt_wav, 16000, device=self.device), 16000)               # resampled once for the tokenizer and the speaker encoder
+            speech_token, speech_token_len = self._extract_speech_token(wav_16k)
+            if resample_rate == 24000:
+                token_len = min(int(speech_feat.shape[1] / 2), speech_token.shape[1])          # force speech_feat = 2 x speech_token (:169-173)
+                # (fresh length tensors, not the reference's in-place writes: the stages return inference-mode tensors)
+                speech_feat, speech_feat_len = speech_feat[:, :2 * token_len], torch.tensor([2 * token_len], dtype=torch.int32, device=self.device)
+                speech_token, speech_token_len = speech_token[:, :token_len], torch.tensor([token_len], dtype=torch.int32, device=self.device)
+            embedding = self._extract_spk_embedding(wav_16k)
+            model_input = {'prompt_text': prompt_text_token, 'prompt_text_len': prompt_text_len,
+                           'llm_prompt_speech_token': speech_token, 'llm_prompt_speech_token_len': speech_token_len,
+                           'flow_prompt_speech_token': speech_token, 'flow_prompt_speech_token_len': speech_token_len,
+                           'prompt_speech_feat': speech_feat, 'prompt_speech_feat_len': speech_feat_len,
+                           'llm_embedding': embedding, 'flow_embedding': embedding}
+        else:
+            model_input = dict(self.spk2info[zero_shot_spk_id])                                # (a copy: the stored entry keeps no request's text)
+        model_input['text'] = text
+        model_input['text_len'] = text_len
+        return model_input

@@ -9,9 +9,12 @@ Mirrors server/model_utils/infer_speech_model.py:
 Model hyper-parameters: the reference builds its modules from `<model_dir>/hydravox.yaml` through HyperPyYAML (:59-62), which is
 not part of this build; yaml_config.py reads the plain numbers of that file (constructor arguments of the `!new:` nodes, `!ref`s
 resolved, Qwen2 sizes from `CosyVoice-BlankEN/config.json`).  `<model_dir>/hvx_config.json`, when present, takes precedence;
-with neither file the [ASSUMED-CV3] preset applies.  The text / audio frontend (ONNX tokenizers, text normalisation) is out of scope: `frontend` is any
-object with the reference's `text_normalize`, `frontend_sft`, `frontend_zero_shot` methods (e.g. the reference's own
-CosyVoiceFrontEnd), injected by the caller.
+with neither file the [ASSUMED-CV3] preset applies.  `frontend` is any object with the reference's `text_normalize`, `frontend_sft`,
+`frontend_zero_shot` methods, built by the caller's `frontend_factory(args, cfg)`.  To serve raw prompt audio (any sample rate) on the device:
+    HvxModelManager(frontend_factory=lambda args, cfg: HvxFrontEnd(tokenize, speech_tokenizer_onnx, campplus_onnx, spk2info))
+(frontend.HvxFrontEnd: resampling, whisper log-mel / kaldi fbank / prompt log-mel and the two ONNX graphs in libhvx; no torchaudio, whisper or
+onnxruntime).  What stays the caller's is the text side: `tokenize(text) -> ids` and, optionally, a text normaliser.  The reference's own
+CosyVoiceFrontEnd fits the same slot where its packages exist.
 """
 import json
 import logging
@@ -60,7 +63,10 @@ def _env_on(name):
 
 class HvxModelManager:
     def __init__(self, frontend_factory=None, flow_fp16=None):
-        """flow_fp16: run the flow decoder in its fp16 mode (HvxFlow(dtype=torch.float16): within 1e-3 of the fp32 reference, the reference's own deployed
+        """frontend_factory(args, cfg) -> the frontend object load_models() stores as `.frontend` (args = load_models' argument, cfg = the HvxConfig read
+        from the model directory); typically `lambda args, cfg: HvxFrontEnd(tokenize, tokenizer_onnx, campplus_onnx, spk2info)`.  None: no frontend, the
+        synthesis functions then fail on the first request.
+        flow_fp16: run the flow decoder in its fp16 mode (HvxFlow(dtype=torch.float16): within 1e-3 of the fp32 reference, the reference's own deployed
         dtype) instead of the bf16 production mode; None = $HVX_FLOW_FP16 (default off)."""
         self.flow_fp16 = _env_on('HVX_FLOW_FP16') if flow_fp16 is None else bool(flow_fp16)
         self.models = None

@@ -6,6 +6,7 @@ import math
 import torch
 
 from . import _lib
+from .packing import sinc_resample_len
 from ._lib import GemmArgs, AttnArgs, LlmAttnArgs, SampleArgs, DecodeGemmArgs, ReduceNormArgs, ptr, stream_ptr, check, dtype_code
 
 
@@ -234,3 +235,17 @@ def resample_linear(x, t_out):
     y = torch.empty(*x.shape[:-1], t_out, dtype=torch.float32, device=x.device)
     check(lib.hvx_op_resample_linear(ptr(x), rows, t_in, ptr(y), t_out, stream_ptr()), 'hvx_op_resample_linear')
     return y
+
+
+def resample_sinc(x, taps_dev, orig, new, width):
+    """torchaudio.transforms.Resample (sinc_interp_hann) of the rows of a float32 (rows, L) device tensor or view (unit stride along L, any row stride):
+    taps_dev = the device table [2 * width + orig][new] of packing.sinc_resample_taps (its taps transposed: the phases of a tap contiguous); orig / new = the
+    rates over their gcd.  -> (rows, ceil(new * L / orig)).  csrc/resample.hip; a geometry the launcher cannot tile raises HvxError."""
+    lib = _lib.load()
+    assert x.dim() == 2 and x.dtype == torch.float32 and (x.shape[1] <= 1 or x.stride(1) == 1), (x.shape, x.dtype, x.stride())
+    assert taps_dev.dtype == torch.float32 and taps_dev.is_contiguous() and tuple(taps_dev.shape) == (2 * width + orig, new), taps_dev.shape
+    rows, L = x.shape
+    out = torch.empty(rows, sinc_resample_len(L, orig, new), dtype=torch.float32, device=x.device)
+    check(lib.hvx_op_resample_sinc(ptr(x), rows, L, x.stride(0) if rows > 1 else L, ptr(taps_dev), orig, new, width, ptr(out), out.shape[1], out.shape[1],
+                                   stream_ptr()), 'hvx_op_resample_sinc')
+    return out

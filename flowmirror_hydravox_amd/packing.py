@@ -274,6 +274,48 @@ def kaldi_fbank_bases(num_mel_bins=80, sample_frequency=16000.0, low_freq=20.0, 
     return ana.float().contiguous(), mel.contiguous()
 
 
+SINC_TAPS_MAX_BYTES = 64 << 20
+
+
+def sinc_resample_taps(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """Polyphase taps of torchaudio.transforms.Resample(orig_freq, new_freq) at its defaults (resampling_method 'sinc_interp_hann'), the resampler
+    cosyvoice/utils/file_utils.py:74 applies to the prompt audio -> (taps f32 [new][K], width, orig, new) with orig, new = the rates over their gcd.
+    torchaudio is not installed here; this is its published algorithm (torchaudio/functional/functional.py: _get_sinc_resample_kernel):
+        base = min(orig, new) * rolloff,  width = ceil(lowpass_filter_width * orig / base),  K = 2 * width + orig
+        t[p][k] = (-p / new + (k - width) / orig) * base, clamped to +-lowpass_filter_width
+        h[p][k] = sinc(pi t) * cos^2(pi t / (2 lowpass_filter_width)) * base / orig,  sinc(0) = 1
+    in float64, cast to float32 at the end.  With x padded by `width` zeros in front and `width + orig` behind,
+        y[j * new + p] = sum_k h[p][k] * xpad[j * orig + k],  cut to ceil(new * L / orig) samples   (csrc/resample.hip).
+    Parity with the package itself is unpinned: in particular its handling of the dtype of the phase offset (it builds the kernel in float64 only when
+    no dtype is passed) cannot be compared here.
+    A pair whose table would exceed 64 MiB (rates with a small gcd, e.g. 44101 -> 16000: 2.8 GB) raises ValueError."""
+    import math
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq <= 0 or new_freq <= 0:
+        raise ValueError('sinc_resample_taps: rates must be positive, got %d -> %d' % (orig_freq, new_freq))
+    g = math.gcd(orig_freq, new_freq)
+    orig, new = orig_freq // g, new_freq // g
+    base = min(orig, new) * rolloff
+    width = int(math.ceil(lowpass_filter_width * orig / base))
+    K = 2 * width + orig
+    if new * K * 4 > SINC_TAPS_MAX_BYTES:
+        raise ValueError('resampling %d Hz -> %d Hz needs a tap table of %d x %d floats (%.1f MiB; the limit is 64 MiB): the rates share too small a divisor'
+                         % (orig_freq, new_freq, new, K, new * K * 4 / 2 ** 20))
+    k = torch.arange(K, dtype=torch.float64)
+    p = torch.arange(new, dtype=torch.float64)
+    t = (-p[:, None] / new + (k[None, :] - width) / orig) * base
+    t = t.clamp(-lowpass_filter_width, lowpass_filter_width)
+    window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    t = t * math.pi
+    h = torch.where(t == 0, torch.ones_like(t), torch.sin(t) / t) * window * (base / orig)
+    return h.float().contiguous(), width, orig, new
+
+
+def sinc_resample_len(length, orig, new):
+    """samples torchaudio's resampler returns for `length` input samples: ceil(new * length / orig), in integers"""
+    return (int(new) * int(length) + int(orig) - 1) // int(orig)
+
+
 def mel_filterbank(sr, n_fft, n_mels, fmin=0.0, fmax=None):
     """librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) with its defaults htk=False, norm='slaney' (librosa is what
     matcha/utils/audio.py:53 calls; it is not installed here, this is its published algorithm): triangular filters on the Slaney mel

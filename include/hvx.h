@@ -152,6 +152,15 @@ int hvx_op_llm_attention(const hvx_llm_attn_args* a, hvx_stream s);
  * inference_zero_shot / text_to_speech (infer_speech_model.py:583-588) and token2wav (cosyvoice/cli/model.py:424-426) */
 int hvx_op_resample_linear(const float* x, int32_t rows, int32_t t_in, float* y, int32_t t_out, hvx_stream s);
 
+/* torchaudio.transforms.Resample(orig_freq, new_freq) with its default sinc_interp_hann kernel, the first step of the zero-shot frontend
+ * (cosyvoice/utils/file_utils.py:46-75), for `rows` fp32 waveforms of `len` samples, row r at x + r * x_row_stride.  orig / new_ are the two rates divided by
+ * their gcd, width = ceil(lowpass_filter_width * orig / (min(orig, new_) * rolloff)), taps the device table [2 * width + orig][new_] (tap-major, the phases of a tap
+ * contiguous) of packing.sinc_resample_taps.  y row r (at y + r * y_row_stride) receives the first out_len <= ceil(new_ * len / orig) samples.  fp32 FMAs over the
+ * taps in ascending order: a sample's bits depend on neither the row count nor the launch.  A geometry that cannot be tiled (a frame of orig + 2 * width floats over
+ * 64 KB, a table over 64 MiB, non-positive sizes, strides shorter than the rows, null pointers, out_len past the bound) returns -1 and launches nothing. */
+int hvx_op_resample_sinc(const float* x, int32_t rows, int32_t len, int64_t x_row_stride, const float* taps, int32_t orig, int32_t new_, int32_t width,
+                         float* y, int32_t out_len, int64_t y_row_stride, hvx_stream s);
+
 /* packs a row-major [N][K] weight into the MFMA fragment order used by the decode GEMMs: [N/16][K/32][64][8] */
 int hvx_op_skinny_gemm(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* Wpacked,
                        const float* bias, int32_t split_k, float* part_ws, float* out_f32, int32_t ldo, hvx_stream s);
