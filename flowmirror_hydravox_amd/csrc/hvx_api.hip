@@ -211,9 +211,11 @@ int hvx_prof_read(int32_t kind, double* sampled_ms, double* sampled_work, int64_
     return 0;
 }
 
-int hvx_ras_sample(const hvx_sample_args* a, hvx_stream s) {
+int hvx_ras_sample_seq(const hvx_sample_args* a, const hvx_seq_sampling* q, hvx_stream s) {
     if (!a) return set_error("hvx_ras_sample: null args"), -1;
+    if (q && (!q->top_k || !q->top_p || !q->win_size || !q->rep_thresh)) return set_error("hvx_ras_sample_seq: the sampling block needs all four arrays"), -1;
     SampleArgs k;
+    memset(&k, 0, sizeof(k));
     k.n_seq = a->n_seq; k.head_k = a->head_k; k.V = a->vocab; k.Vs = a->speech_tokens;
     k.logp = a->logp; k.logp_ss = a->logp_seq_stride; k.logp_hs = a->logp_head_stride;
     k.hist = a->hist; k.hist_ss = a->hist_seq_stride; k.hist_len = a->hist_len;
@@ -221,8 +223,11 @@ int hvx_ras_sample(const hvx_sample_args* a, hvx_stream s) {
     k.top_k = a->top_k; k.top_p = a->top_p; k.win_size = a->win_size; k.rep_thresh = a->rep_thresh;
     k.noise = a->noise; k.noise_ss = a->noise_seq_stride; k.noise_len = a->noise_len; k.noise_limit = (const long long*)a->noise_limit;
     k.cursor = (long long*)a->cursor; k.out_ids = a->out_ids; k.max_trials = a->max_trials;
+    if (q) { k.seq_top_k = q->top_k; k.seq_top_p = q->top_p; k.seq_win = q->win_size; k.seq_thresh = q->rep_thresh; }
     return launch_ras_sample(k, (hipStream_t)s);
 }
+
+int hvx_ras_sample(const hvx_sample_args* a, hvx_stream s) { return hvx_ras_sample_seq(a, nullptr, s); }
 
 int hvx_op_gemm(const hvx_gemm_args* a, hvx_stream s) {
     if (!a) return set_error("hvx_op_gemm: null args"), -1;

@@ -253,6 +253,9 @@ struct SampleArgs {
     long long* cursor;                      // in/out per seq: next unread noise value
     int* out_ids;                           // [n_seq][head_k]; -1 = max_trials exhausted, -2 = noise exhausted (cursor unchanged)
     int max_trials;
+    // optional per-sequence sampling parameters, [n_seq] each, all four or none (none: the scalars above serve every sequence).  The kernel
+    // clamps seq_top_k to [1, MAX_CAND] itself: a device array cannot be validated at launch.
+    const int* seq_top_k; const float* seq_top_p; const int* seq_win; const int* seq_thresh;
 };
 int launch_ras_sample(const SampleArgs& a, hipStream_t s);
 
@@ -265,9 +268,17 @@ struct AdvanceArgs {
     int* hist; int* hist_len; int* min_adj; int* active;
     int* seq_state;                         // [n_seq][8]: pos, out_len, done, min_len, max_len, steps, err, -
     int* out_tokens;                        // [n_seq][max_out]
+    // optional per-sequence sampling parameters (SampleArgs: seq_*).  With them a sequence's repetition ring is seq_win[i] entries long
+    // (clamped to [1, win_cap]) instead of win_cap: the ring then holds exactly the window the sampler counts over, wrapped or not.
+    int* seq_top_k; float* seq_top_p; int* seq_win; int* seq_thresh;
+};
+// the four per-sequence sampling values a joining sequence brings along (written by the join kernel beside the rest of the slot's state)
+struct SeqSampling {
+    int top_k; float top_p; int win_size; int rep_thresh;
 };
 int launch_decode_advance(const AdvanceArgs& a, hipStream_t s);
-int launch_decode_join(const AdvanceArgs& a, long long* cursor, int slot, int first_tok, int pos, int min_len, int max_len, hipStream_t s);
+int launch_decode_join(const AdvanceArgs& a, long long* cursor, int slot, int first_tok, int pos, int min_len, int max_len, hipStream_t s,
+                       const SeqSampling* q = nullptr);
 
 // ------------------------------------------------------------------------------------------------
 // HiFT source / STFT / iSTFT

@@ -41,6 +41,7 @@ struct hvx_llm {
     std::map<GraphKey, hipGraphExec_t> graphs;
     struct StepGraph {
         hvx_decode_args a;
+        hvx_seq_sampling q;                  // (all NULL: the scalar form)
         hipStream_t s;
         hipGraphExec_t ex;
     };
@@ -257,7 +258,13 @@ int hvx_llm_forward(hvx_llm* h, hvx_stream stream, int32_t n_seq, int32_t kn, co
     return 0;
 }
 
-static int decode_step_impl(hvx_llm* h, hipStream_t s, const hvx_decode_args& a) {
+static void set_seq(AdvanceArgs& aa, const hvx_seq_sampling& q) {
+    // (the join kernel is the one writer of these arrays; the header declares them const for the readers)
+    aa.seq_top_k = const_cast<int*>(q.top_k); aa.seq_top_p = const_cast<float*>(q.top_p);
+    aa.seq_win = const_cast<int*>(q.win_size); aa.seq_thresh = const_cast<int*>(q.rep_thresh);
+}
+
+static int decode_step_impl(hvx_llm* h, hipStream_t s, const hvx_decode_args& a, const hvx_seq_sampling& q) {
     if (forward_impl(h, s, a.n_seq, a.head_k, a.tok, a.ctrl, a.head_k, a.logp)) return -1;
     SampleArgs sa;
     memset(&sa, 0, sizeof(sa));
@@ -267,33 +274,45 @@ static int decode_step_impl(hvx_llm* h, hipStream_t s, const hvx_decode_args& a)
     sa.top_k = a.top_k; sa.top_p = a.top_p; sa.win_size = a.win_size; sa.rep_thresh = a.rep_thresh;
     sa.noise = a.noise; sa.noise_ss = a.noise_seq_stride; sa.noise_len = a.noise_len; sa.noise_limit = (const long long*)a.noise_limit; sa.cursor = (long long*)a.cursor;
     sa.out_ids = a.ids; sa.max_trials = a.max_trials;
+    sa.seq_top_k = q.top_k; sa.seq_top_p = q.top_p; sa.seq_win = q.win_size; sa.seq_thresh = q.rep_thresh;
     if (launch_ras_sample(sa, s)) return -1;
     AdvanceArgs aa;
     memset(&aa, 0, sizeof(aa));
     aa.n_seq = a.n_seq; aa.head_k = a.head_k; aa.win_cap = a.win_cap; aa.max_out = a.max_out; aa.speech_tokens = h->c.speech_tokens;
     aa.ids = a.ids; aa.tok = a.tok; aa.ctrl = a.ctrl; aa.hist = a.hist; aa.hist_len = a.hist_len; aa.min_adj = a.min_adj; aa.active = a.active;
     aa.seq_state = a.seq_state; aa.out_tokens = a.out_tokens;
+    set_seq(aa, q);
     return launch_decode_advance(aa, s);
 }
 
 int hvx_llm_decode_steps(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, int32_t n_steps) {
+    return hvx_llm_decode_steps_seq(h, stream, a, nullptr, n_steps);
+}
+
+int hvx_llm_decode_steps_seq(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, const hvx_seq_sampling* qp, int32_t n_steps) {
     if (!h || !h->ws || !a) return set_error("hvx_llm_decode_steps: handle not bound / null argument"), -1;
+    hvx_seq_sampling q;
+    memset(&q, 0, sizeof(q));
+    if (qp) {
+        if (!qp->top_k || !qp->top_p || !qp->win_size || !qp->rep_thresh) return set_error("hvx_llm_decode_steps_seq: the sampling block needs all four arrays"), -1;
+        q = *qp;
+    }
     if (a->n_seq < 1 || a->head_k < 1 || a->head_k > 8 || a->win_cap < 1 || a->max_out < 1 || !a->tok || !a->ctrl || !a->hist || !a->hist_len ||
         !a->min_adj || !a->active || !a->seq_state || !a->out_tokens || !a->ids || !a->logp || !a->noise || !a->cursor)
         return set_error("hvx_llm_decode_steps: bad argument block"), -1;
     hipStream_t s = (hipStream_t)stream;
     if (!h->use_graph || prof_enabled() || s == nullptr) {
         for (int i = 0; i < n_steps; ++i)
-            if (decode_step_impl(h, s, *a)) return -1;
+            if (decode_step_impl(h, s, *a, q)) return -1;
         return 0;
     }
     hipGraphExec_t ex = nullptr;
     for (auto& g : h->step_graphs)
-        if (g.s == s && memcmp(&g.a, a, sizeof(*a)) == 0) ex = g.ex;
+        if (g.s == s && memcmp(&g.a, a, sizeof(*a)) == 0 && memcmp(&g.q, &q, sizeof(q)) == 0) ex = g.ex;
     if (!ex) {
         hipGraph_t g = nullptr;
         if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return set_error("hvx_llm_decode_steps: begin capture failed"), -1;
-        const int rc = decode_step_impl(h, s, *a);
+        const int rc = decode_step_impl(h, s, *a, q);
         const hipError_t e = hipStreamEndCapture(s, &g);
         if (rc != 0 || e != hipSuccess || !g) {
             if (g) hipGraphDestroy(g);
@@ -311,6 +330,7 @@ int hvx_llm_decode_steps(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a
         }
         hvx_llm::StepGraph sg;
         memcpy(&sg.a, a, sizeof(*a));                         // (byte copy: padding is compared too, callers pass a zeroed block)
+        memcpy(&sg.q, &q, sizeof(q));
         sg.s = s;
         sg.ex = ex;
         h->step_graphs.push_back(sg);
@@ -320,8 +340,8 @@ int hvx_llm_decode_steps(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a
     return 0;
 }
 
-int hvx_llm_decode_join(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, int32_t slot, int32_t first_tok, int32_t pos,
-                        int32_t min_len, int32_t max_len) {
+static int decode_join_impl(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, const hvx_seq_sampling* q, const SeqSampling* v, int32_t slot,
+                            int32_t first_tok, int32_t pos, int32_t min_len, int32_t max_len) {
     if (!h || !h->ws || !a) return set_error("hvx_llm_decode_join: handle not bound / null argument"), -1;
     if (slot < 0 || slot >= a->n_seq || slot >= h->n_slots || pos < 0 || pos + 1 > h->max_ctx || !a->cursor)
         return set_error("hvx_llm_decode_join: slot %d / position %d outside the bound grid", slot, pos), -1;
@@ -330,7 +350,26 @@ int hvx_llm_decode_join(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a,
     aa.n_seq = a->n_seq; aa.head_k = a->head_k; aa.win_cap = a->win_cap; aa.max_out = a->max_out; aa.speech_tokens = h->c.speech_tokens;
     aa.ids = a->ids; aa.tok = a->tok; aa.ctrl = a->ctrl; aa.hist = a->hist; aa.hist_len = a->hist_len; aa.min_adj = a->min_adj; aa.active = a->active;
     aa.seq_state = a->seq_state; aa.out_tokens = a->out_tokens;
-    return launch_decode_join(aa, (long long*)a->cursor, slot, first_tok, pos, min_len, max_len, (hipStream_t)stream);
+    if (q) set_seq(aa, *q);
+    return launch_decode_join(aa, (long long*)a->cursor, slot, first_tok, pos, min_len, max_len, (hipStream_t)stream, v);
+}
+
+int hvx_llm_decode_join(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, int32_t slot, int32_t first_tok, int32_t pos,
+                        int32_t min_len, int32_t max_len) {
+    return decode_join_impl(h, stream, a, nullptr, nullptr, slot, first_tok, pos, min_len, max_len);
+}
+
+int hvx_llm_decode_join_seq(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, const hvx_seq_sampling* q, int32_t slot, int32_t first_tok,
+                            int32_t pos, int32_t min_len, int32_t max_len, int32_t top_k, float top_p, int32_t win_size, int32_t rep_thresh) {
+    if (!a || !q || !q->top_k || !q->top_p || !q->win_size || !q->rep_thresh)
+        return set_error("hvx_llm_decode_join_seq: null argument / the sampling block needs all four arrays"), -1;
+    // refused here, before anything is enqueued: the kernels can only clamp what they find in the arrays
+    if (top_k < 1 || top_k > 64) return set_error("hvx_llm_decode_join_seq: top_k=%d outside [1,64]", top_k), -1;
+    if (!(top_p > 0.0f)) return set_error("hvx_llm_decode_join_seq: top_p=%g must be positive", (double)top_p), -1;
+    if (win_size < 1 || win_size > a->win_cap) return set_error("hvx_llm_decode_join_seq: win_size=%d outside [1,win_cap=%d]", win_size, a->win_cap), -1;
+    if (rep_thresh < 0) return set_error("hvx_llm_decode_join_seq: rep_thresh=%d is negative", rep_thresh), -1;
+    const SeqSampling v{top_k, top_p, win_size, rep_thresh};
+    return decode_join_impl(h, stream, a, q, &v, slot, first_tok, pos, min_len, max_len);
 }
 
 int hvx_llm_use_graph(hvx_llm* h, int32_t enable) {

@@ -102,7 +102,20 @@ __global__ __launch_bounds__(256) void ras_sample_kernel(SampleArgs a) {
     const int hist_len = a.hist_len[s];
     const int* hist = a.hist + (long long)s * a.hist_ss;
     const int min_len = a.min_len[s];
-    const int win = (a.win_size == 0) ? hist_len : min(a.win_size, hist_len);
+    // The sampling parameters of this sequence, read ONCE: the candidate loop and the trial loop below run block_best / __syncthreads under
+    // bounds made of them, so they must be the same value in every thread of the workgroup — every thread loads the same address, and the
+    // first lane's copy is what all of them use (a wave-uniform register by construction; the four waves read the same words).
+    int top_k = a.top_k, win_size = a.win_size, rep_thresh = a.rep_thresh;
+    float top_p = a.top_p;
+    if (a.seq_top_k) {
+        top_k = __builtin_amdgcn_readfirstlane(a.seq_top_k[s]);
+        top_p = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a.seq_top_p[s])));
+        win_size = __builtin_amdgcn_readfirstlane(a.seq_win[s]);
+        rep_thresh = __builtin_amdgcn_readfirstlane(a.seq_thresh[s]);
+        top_k = min(max(top_k, 1), MAX_CAND);                // (the scalar is validated by launch_ras_sample; an array cannot be)
+        win_size = max(win_size, 0);
+    }
+    const int win = (win_size == 0) ? hist_len : min(win_size, hist_len);
     bool overflow = false;
     // Everything the trial loops will touch is requested up front, beside the first head's logits: the repetition window (shared by
     // the K heads, llm_multi_head_v3.py:891-900) and the next NW noise values (a step without EOS retries consumes <= K * top_k).
@@ -158,8 +171,8 @@ __global__ __launch_bounds__(256) void ras_sample_kernel(SampleArgs a) {
         Best mine = local_best();
         int n = 0;
         float cum = 0.0f;
-        const int kmax = min(min(a.top_k, MAX_CAND), V);
-        while (cum < a.top_p && n < kmax) {
+        const int kmax = min(min(top_k, MAX_CAND), V);
+        while (cum < top_p && n < kmax) {
             const Best wv = block_best(mine, red_v, red_i);
             if (tid == 0) {
                 cand_v[n] = wv.v;
@@ -199,7 +212,7 @@ __global__ __launch_bounds__(256) void ras_sample_kernel(SampleArgs a) {
             if ((tid & 63) == 0) red_i[tid >> 6] = rep;
             __syncthreads();
             rep = red_i[0] + red_i[1] + red_i[2] + red_i[3];
-            if (rep >= a.rep_thresh) {
+            if (rep >= rep_thresh) {
                 // random_sampling: race over the full vocabulary (common.py:164-166)
                 if (cursor + V > limit) {
                     overflow = true;
@@ -245,7 +258,12 @@ __global__ __launch_bounds__(256) void ras_sample_kernel(SampleArgs a) {
 
 int launch_ras_sample(const SampleArgs& a, hipStream_t s) {
     if (a.n_seq <= 0) return 0;
-    if (a.top_k < 1 || a.top_k > MAX_CAND) {
+    const int n_seq_arrays = (a.seq_top_k != nullptr) + (a.seq_top_p != nullptr) + (a.seq_win != nullptr) + (a.seq_thresh != nullptr);
+    if (n_seq_arrays != 0 && n_seq_arrays != 4) {
+        set_error("ras_sample: per-sequence sampling needs all four arrays (top_k, top_p, win_size, rep_thresh), got %d", n_seq_arrays);
+        return -1;
+    }
+    if (n_seq_arrays == 0 && (a.top_k < 1 || a.top_k > MAX_CAND)) {
         set_error("ras_sample: top_k=%d outside [1,%d]", a.top_k, MAX_CAND);
         return -1;
     }
@@ -277,6 +295,8 @@ __global__ void decode_advance_kernel(AdvanceArgs a) {
     int pos = st[0], out_len = st[1], done = st[2];
     const int min_len = st[3], max_len = st[4];
     int n_next = 0;
+    // ring length of this sequence: the engine-wide capacity, or the sequence's own window (see AdvanceArgs)
+    const int ring = a.seq_win ? min(max(a.seq_win[i], 1), a.win_cap) : a.win_cap;
     if (!done && a.ids[i * K] == -2) {
         // the sampler ran out of pre-generated noise for this sequence (all K ids are -2, its cursor is untouched): the step is void.
         // Nothing advances — the same rows are fed again (rewriting the same KV entries) until the host has refilled the window.
@@ -298,7 +318,7 @@ __global__ void decode_advance_kernel(AdvanceArgs a) {
                 break;
             }
             if (out_len < a.max_out) a.out_tokens[(long long)i * a.max_out + out_len] = t;
-            a.hist[(long long)i * a.win_cap + (out_len % a.win_cap)] = t;
+            a.hist[(long long)i * a.win_cap + (out_len % ring)] = t;
             a.tok[i * K + n_next] = t;
             ++out_len;
             ++n_next;
@@ -317,7 +337,7 @@ __global__ void decode_advance_kernel(AdvanceArgs a) {
     a.ctrl[2 * a.n_seq + i] = nn;
     a.ctrl[3 * a.n_seq + i] = pos + nn;
     a.ctrl[4 * a.n_seq + i] = nn ? (i * K + nn - 1) : -1;
-    const int hl = out_len < a.win_cap ? out_len : a.win_cap;
+    const int hl = out_len < ring ? out_len : ring;
     a.hist_len[i] = hl;
     a.min_adj[i] = min_len - (out_len - hl);
     a.active[i] = done ? 0 : 1;
@@ -328,8 +348,14 @@ __global__ void decode_advance_kernel(AdvanceArgs a) {
 
 // A new sequence takes over slot i of a running decode grid (continuous batching): what the host-side set-up of a batch writes for
 // every sequence, for one slot, ordered on the stream between two steps.  Its prefix but the last row is already in the slot's KV cache.
-__global__ void decode_join_kernel(AdvanceArgs a, long long* cursor, int i, int first_tok, int pos, int min_len, int max_len) {
+__global__ void decode_join_kernel(AdvanceArgs a, long long* cursor, int i, int first_tok, int pos, int min_len, int max_len, int has_q, SeqSampling q) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (has_q) {                                             // the slot's own sampling parameters: its predecessor's are history from here on
+        a.seq_top_k[i] = q.top_k;
+        a.seq_top_p[i] = q.top_p;
+        a.seq_win[i] = q.win_size;
+        a.seq_thresh[i] = q.rep_thresh;
+    }
     const int K = a.head_k;
     a.tok[i * K] = first_tok;
     for (int j = 1; j < K; ++j) a.tok[i * K + j] = -1;
@@ -346,8 +372,10 @@ __global__ void decode_join_kernel(AdvanceArgs a, long long* cursor, int i, int 
     cursor[i] = 0;
 }
 
-int launch_decode_join(const AdvanceArgs& a, long long* cursor, int slot, int first_tok, int pos, int min_len, int max_len, hipStream_t s) {
-    hipLaunchKernelGGL(decode_join_kernel, dim3(1), dim3(64), 0, s, a, cursor, slot, first_tok, pos, min_len, max_len);
+int launch_decode_join(const AdvanceArgs& a, long long* cursor, int slot, int first_tok, int pos, int min_len, int max_len, hipStream_t s,
+                       const SeqSampling* q) {
+    if (q && (!a.seq_top_k || !a.seq_top_p || !a.seq_win || !a.seq_thresh)) return set_error("decode_join: per-sequence values without the four arrays"), -1;
+    hipLaunchKernelGGL(decode_join_kernel, dim3(1), dim3(64), 0, s, a, cursor, slot, first_tok, pos, min_len, max_len, q ? 1 : 0, q ? *q : SeqSampling{0, 0.0f, 0, 0});
     return hipGetLastError() == hipSuccess ? 0 : (set_error("decode_join launch failed"), -1);
 }
 

@@ -48,6 +48,21 @@ class _Request:
         self.done = False
         self.cursor = 0                   # absolute noise position
         self.pos = 0                      # KV length
+        self.sp = None                    # own sampling parameters (a mixed-sampling grid): normalised dict, None = the engine's defaults
+        self.thr = None                   # rep_threshold(win_size, tau_r) of those
+        self.sp_error = None              # what was wrong with the parameters the request came with
+
+    def set_sampling(self, sampling):
+        """the request's own top_p / top_k / win_size / tau_r, in any form sampling_params accepts; a bad set is kept as the request's error"""
+        try:
+            self.sp = sampling_params(sampling)
+            if not self.sp['top_p'] > 0:
+                raise ValueError('top_p=%r must be positive' % self.sp['top_p'])
+            if self.sp['win_size'] < 0 or self.sp['tau_r'] < 0:
+                raise ValueError('win_size=%r / tau_r=%r must not be negative' % (self.sp['win_size'], self.sp['tau_r']))
+            self.thr = rep_threshold(self.sp['win_size'], self.sp['tau_r'])
+        except (ValueError, TypeError, KeyError) as e:
+            self.sp, self.thr, self.sp_error = None, None, ValueError('sampling parameters refused: %s' % e)
 
 
 class HvxLLM:
@@ -306,12 +321,17 @@ class HvxLLM:
         self.last_stats = eng.stats
 
     @torch.inference_mode()
-    def generate_stream(self, requests, n_slots=None, max_out=None, max_prefix=None, pace=None):
+    def generate_stream(self, requests, n_slots=None, max_out=None, max_prefix=None, pace=None, mixed_sampling=False, win_cap=None):
         """Continuous batching (replaces the one-request-at-a-time loop of server/worker.py:54-102): `requests` is an
         iterable of dicts (text, prompt_text, prompt_speech_token, seed, max_token_text_ratio, min_token_text_ratio, tag).  Up to `n_slots`
         sequences share one decode grid — the weights are streamed once per step for all of them — and the slot of a finished sequence is
         taken over by the next waiting request between two blocks of steps (prefill into the slot's KV cache + hvx_llm_decode_join).
-        Yields (tag, token list) in completion order.  A request's ids do not depend on what else is in flight (own noise stream)."""
+        Yields (tag, token list) in completion order.  A request's ids do not depend on what else is in flight (own noise stream).
+        mixed_sampling: the sampling parameters are per-sequence state of the grid — a request dict may carry `sampling` (a dict or partial of
+        top_p / top_k / win_size / tau_r, as `llm.sampling` takes them; without it the request samples with `llm.sampling`), and requests with
+        different parameters decode side by side, each exactly as if it were served alone with its parameters on `llm.sampling`.  `win_cap`
+        (default 64) is the longest repetition window such a grid holds; a request with a longer one, or with win_size 0 (whole history),
+        comes back with its error."""
         n_slots = n_slots or self.max_batch
 
         def to_req(d):
@@ -321,6 +341,8 @@ class HvxLLM:
             r = _Request(self._encode_prefix(text, None if pt is None else torch.as_tensor(pt), None if ps is None else torch.as_tensor(ps)), n_text,
                          int(n_text * d.get('min_token_text_ratio', 2)), int(n_text * d.get('max_token_text_ratio', 20)), NoiseStream(seed=d['seed'] if d.get('seed') is not None else _fresh_seed(), chunk=8192))
             r.tag = d.get('tag')
+            if d.get('sampling') is not None:
+                r.set_sampling(d['sampling'])
             return r
         if hasattr(requests, 'poll'):
             # an open-ended polling source (the queue worker): poll(block) -> request dict | None, StopIteration when closed
@@ -341,7 +363,7 @@ class HvxLLM:
                 max_out = max([r.max_len for r in it] + [1])
                 max_prefix = max([len(r.prefix) for r in it] + [1])
                 it = iter(it)
-        eng = _DecodeEngine(self, n_slots=n_slots, max_out=max_out, max_prefix=max_prefix, pace=pace)
+        eng = _DecodeEngine(self, n_slots=n_slots, max_out=max_out, max_prefix=max_prefix, pace=pace, mixed_sampling=mixed_sampling, win_cap=win_cap)
         gen = eng.run(it)
         try:
             for kind, r in gen:
@@ -397,8 +419,15 @@ class _DecodeEngine:
     PREFILL_GROUP = 8              # prefixes per grouped prefill forward, at most (8 x 514 rows = the GEMMs' efficient range; llm.prefill_group = 1: every prefix alone — A / B)
     PREFILL_ROWS = 8 * 528         # row budget of one grouped forward: the workspace is bound for max(max_prefix, this), whatever max_prefix is — a group of n-row prefixes holds PREFILL_ROWS // n members
 
-    def __init__(self, llm, n_slots, max_out, max_prefix, stream_first=False, sync_every=None, pace=None):
+    MIXED_WIN_CAP = 64             # default ring capacity of a mixed-sampling grid (the sampler's LDS snapshot holds 256 entries: anything up to that stays on its fast path)
+
+    def __init__(self, llm, n_slots, max_out, max_prefix, stream_first=False, sync_every=None, pace=None, mixed_sampling=False, win_cap=None):
         import time
+        self.mixed = bool(mixed_sampling)
+        if not self.mixed and win_cap is not None:
+            raise ValueError('win_cap belongs to a mixed-sampling grid (mixed_sampling=True)')
+        if self.mixed and win_cap is not None and int(win_cap) < 1:
+            raise ValueError('win_cap=%r must be at least 1' % (win_cap,))
         self.pace = tuple(int(v) for v in pace) if pace else None
         if self.pace is not None and (len(self.pace) != 3 or self.pace[0] < 1 or self.pace[1] < 1 or self.pace[2] < 0):
             raise ValueError('pace = (first >= 1, every_steps >= 1, more >= 0), got %r' % (pace,))       # (first == 0 would leave the idle grid spinning)
@@ -422,6 +451,9 @@ class _DecodeEngine:
         self.stream = llm._stream
         self.stream.wait_stream(torch.cuda.current_stream())
         self.W = max(self.sp['win_size'] if self.sp['win_size'] > 0 else self.max_out, 1)
+        if self.mixed:
+            # per-sequence windows: every slot's ring is as long as its own window, inside rows of `win_cap` entries
+            self.W = int(win_cap) if win_cap is not None else self.MIXED_WIN_CAP
         W = self.W
         with torch.cuda.stream(self.stream):
             # (rows for a grouped prefill: up to PREFILL_GROUP prefixes of equal length go through the backbone in ONE forward — see _prefill_group)
@@ -453,7 +485,20 @@ class _DecodeEngine:
             self.head = [0] * S                  # absolute position up to which slot i's ring is filled
             self.limit_dev = torch.zeros(S, dtype=torch.int64, device=dev)
             self.cur_dev = torch.zeros(S, dtype=torch.int64, device=dev)
+            self.seq = None
+            if self.mixed:
+                # the four sampling numbers per slot, at fixed addresses like the rest of the decode state: hvx_llm_decode_join_seq writes a
+                # slot's row, the captured step reads it.  Empty slots hold the engine's defaults (window clamped into the ring).
+                sp = self.sp
+                self.seq_top_k = torch.full((S,), sp['top_k'], dtype=torch.int32, device=dev)
+                self.seq_top_p = torch.full((S,), sp['top_p'], dtype=torch.float32, device=dev)
+                self.seq_win = torch.full((S,), min(max(sp['win_size'], 1), W), dtype=torch.int32, device=dev)
+                self.seq_thr = torch.full((S,), max(self.thr, 0), dtype=torch.int32, device=dev)
+                self.seq = _lib.SeqSampling()
+                self.seq.top_k, self.seq.top_p = self.seq_top_k.data_ptr(), self.seq_top_p.data_ptr()
+                self.seq.win_size, self.seq.rep_thresh = self.seq_win.data_ptr(), self.seq_thr.data_ptr()
         self.slot_req = [None] * S
+        self.joins = []                          # (tag, slot) of every request that joined, in order
         self.join_block = [0] * S                # blocks launched when the slot's request joined: older snapshots describe its predecessor
         self.last_fill = [0] * S
         self._keep = []                          # pinned arena chunks of the small asynchronous copies (see _h2d)
@@ -505,8 +550,24 @@ class _DecodeEngine:
     def _publish_limits(self):
         self.limit_dev.copy_(self._h2d(self.head, torch.int64), non_blocking=True)     # behind the data, on the same stream
 
+    def _sampling_of(self, r):
+        """(parameters, repetition threshold) request r samples with: its own, or the engine's defaults"""
+        return (self.sp, self.thr) if r.sp is None else (r.sp, r.thr)
+
     def _refuse(self, r):
         """None, or the error that keeps request r off the grid"""
+        if getattr(r, 'sp_error', None) is not None:
+            return r.sp_error
+        if getattr(r, 'sp', None) is not None and not self.mixed:
+            return ValueError('the request carries its own sampling parameters but the decode grid was not started with mixed_sampling=True')
+        if self.mixed:
+            sp, _ = self._sampling_of(r)
+            if sp['win_size'] == 0:
+                return ValueError('win_size=0 (whole history) cannot join a mixed-sampling grid')
+            if not (1 <= sp['win_size'] <= self.W):
+                return ValueError("win_size=%d exceeds the grid's win_cap=%d" % (sp['win_size'], self.W))
+            if not sp['top_p'] > 0:
+                return ValueError('top_p=%r must be positive' % sp['top_p'])
         if len(r.prefix) + r.max_len + self.K > self.llm.max_ctx:
             return ValueError('context %d exceeds max_ctx=%d' % (len(r.prefix) + r.max_len + self.K, self.llm.max_ctx))
         if r.max_len > self.max_out:
@@ -541,9 +602,15 @@ class _DecodeEngine:
             ctrl = self._h2d([i, 0, n, n, n - 1], torch.int32)
             llm._forward(1, n, tok, ctrl, 0, None)
         r.pos = n
-        check(llm.lib.hvx_llm_decode_join(llm._h, C.c_void_p(self.stream.cuda_stream), C.byref(self.args), i, int(r.prefix[-1]), n, r.min_len, r.max_len),
-              'hvx_llm_decode_join')
+        if self.mixed:
+            sp, thr = self._sampling_of(r)
+            check(llm.lib.hvx_llm_decode_join_seq(llm._h, C.c_void_p(self.stream.cuda_stream), C.byref(self.args), C.byref(self.seq), i, int(r.prefix[-1]), n,
+                                                  r.min_len, r.max_len, sp['top_k'], sp['top_p'], sp['win_size'], thr), 'hvx_llm_decode_join_seq')
+        else:
+            check(llm.lib.hvx_llm_decode_join(llm._h, C.c_void_p(self.stream.cuda_stream), C.byref(self.args), i, int(r.prefix[-1]), n, r.min_len, r.max_len),
+                  'hvx_llm_decode_join')
         self.slot_req[i] = r
+        self.joins.append((getattr(r, 'tag', None), i))
         self.join_block[i] = launched
         self.head[i] = 0
         # the whole ring at once (~2.5 ms of host time per request): filling a first slice only and topping the rest up behind the first
@@ -599,7 +666,11 @@ class _DecodeEngine:
             with torch.cuda.stream(stream):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
-                check(llm.lib.hvx_llm_decode_steps(llm._h, C.c_void_p(stream.cuda_stream), C.byref(self.args), sync_every), 'hvx_llm_decode_steps')
+                if self.mixed:
+                    check(llm.lib.hvx_llm_decode_steps_seq(llm._h, C.c_void_p(stream.cuda_stream), C.byref(self.args), C.byref(self.seq), sync_every),
+                          'hvx_llm_decode_steps_seq')
+                else:
+                    check(llm.lib.hvx_llm_decode_steps(llm._h, C.c_void_p(stream.cuda_stream), C.byref(self.args), sync_every), 'hvx_llm_decode_steps')
                 e1.record(stream)
                 live = [r for r in self.slot_req if r is not None and not r.done]
                 blocks.append((e0, e1, len(live), sum(r.state[0] for r in live)))
@@ -812,7 +883,9 @@ class _DecodeEngine:
                               requests=n_done, prefill_and_setup_seconds=t_setup,
                               device_idle_ms_between_blocks=sum(gaps), idle_gaps_over_1ms=[(i, round(g, 1)) for i, g in enumerate(gaps) if g > 1.0][:24], decode_step_us=1e3 * step_ms, decode_steps_timed=n_blk * sync_every,
                               mean_active_sequences=seqs, mean_ctx=ctx_sum / seqs if seqs else 0.0,
-                              decode_step_bytes=llm.decode_step_bytes(1, K, ctx_sum), clean=finished_clean)
+                              decode_step_bytes=llm.decode_step_bytes(1, K, ctx_sum), clean=finished_clean, mixed_sampling=self.mixed)
+            if self.mixed:
+                self.stats['joins'] = list(self.joins)        # (tag, slot) in join order: which request took over whose slot
 
 
 @torch.inference_mode()

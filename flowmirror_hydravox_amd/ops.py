@@ -207,10 +207,39 @@ def reduce_rmsnorm(x, *, M, H, ldx, part=None, split_k=0, part_stride=0, part_zs
     check(lib.hvx_op_reduce_rmsnorm(C.byref(a), stream_ptr()), 'hvx_op_reduce_rmsnorm')
 
 
-def ras_sample(logp, hist, hist_len, min_len, noise, cursor, *, speech_tokens, top_k, top_p, win_size, rep_thresh, active=None,
-               max_trials=100):
+SEQ_PARAM_KEYS = ('top_k', 'top_p', 'win_size', 'rep_thresh')
+
+
+def seq_sampling_block(seq_params, n_seq, device):
+    """dict of four [n_seq] tensors (top_k int32, top_p float32, win_size int32, rep_thresh int32) -> (_lib.SeqSampling, the device tensors it
+    points to).  Validated on the host before anything is launched: the kernel can only clamp what it finds in a device array."""
+    if sorted(seq_params) != sorted(SEQ_PARAM_KEYS):
+        raise ValueError('seq_params needs exactly %s, got %s' % (list(SEQ_PARAM_KEYS), sorted(seq_params)))
+    host = {k: torch.as_tensor(seq_params[k]).detach().cpu().reshape(-1) for k in SEQ_PARAM_KEYS}
+    for k, v in host.items():
+        if v.numel() != n_seq:
+            raise ValueError('seq_params[%r] has %d entries for %d sequences' % (k, v.numel(), n_seq))
+    if n_seq:
+        tk, tp, ws, th = (host[k] for k in SEQ_PARAM_KEYS)
+        if int(tk.min()) < 1 or int(tk.max()) > 64:
+            raise ValueError('seq_params top_k outside [1, 64]')
+        if not bool((tp.double() > 0).all()):
+            raise ValueError('seq_params top_p must be positive')
+        if int(ws.min()) < 0:
+            raise ValueError('seq_params win_size is negative')
+        if int(th.min()) < 0:
+            raise ValueError('seq_params rep_thresh is negative')
+    dev = {k: host[k].to(torch.float32 if k == 'top_p' else torch.int32).contiguous().to(device) for k in SEQ_PARAM_KEYS}
+    q = _lib.SeqSampling()
+    q.top_k, q.top_p, q.win_size, q.rep_thresh = (dev[k].data_ptr() for k in SEQ_PARAM_KEYS)
+    return q, dev
+
+
+def ras_sample(logp, hist, hist_len, min_len, noise, cursor, *, speech_tokens, top_k=25, top_p=0.8, win_size=10, rep_thresh=1, active=None,
+               max_trials=100, seq_params=None, seq_entry=None):
     """logp f32 [S][K][V]; hist int32 [S][Hcap]; hist_len/min_len int32 [S]; noise f32 [S][Ncap]; cursor int64 [S] (updated in place)
-    -> ids int32 [S][K]"""
+    -> ids int32 [S][K].  seq_params: dict of four [S] tensors (top_k, top_p, win_size, rep_thresh) — every sequence samples with its own
+    values and the scalar keywords are not read (hvx_ras_sample_seq).  seq_entry=True takes that entry point with a NULL block."""
     lib = _lib.load()
     S, K, V = logp.shape
     out = torch.empty(S, K, dtype=torch.int32, device=logp.device)
@@ -222,7 +251,13 @@ def ras_sample(logp, hist, hist_len, min_len, noise, cursor, *, speech_tokens, t
     a.top_k, a.top_p, a.win_size, a.rep_thresh = top_k, top_p, win_size, rep_thresh
     a.noise, a.noise_seq_stride, a.noise_len = ptr(noise), noise.shape[1], noise.shape[1]
     a.cursor, a.out_ids, a.max_trials = ptr(cursor), ptr(out), max_trials
-    check(lib.hvx_ras_sample(C.byref(a), stream_ptr()), 'hvx_ras_sample')
+    if seq_params is not None:
+        q, keep = seq_sampling_block(seq_params, S, logp.device)      # (`keep`: the arrays live until the launch is enqueued; the allocator reuses them in stream order)
+        check(lib.hvx_ras_sample_seq(C.byref(a), C.byref(q), stream_ptr()), 'hvx_ras_sample_seq')
+    elif seq_entry:
+        check(lib.hvx_ras_sample_seq(C.byref(a), None, stream_ptr()), 'hvx_ras_sample_seq')
+    else:
+        check(lib.hvx_ras_sample(C.byref(a), stream_ptr()), 'hvx_ras_sample')
     return out
 
 

@@ -32,6 +32,7 @@ class Utterance:
     tag: object = None                                      # caller's handle (a queue task, ...), returned with the result
     max_token_text_ratio: Optional[float] = None            # per-utterance overrides of the call's length ratios
     min_token_text_ratio: Optional[float] = None
+    sampling: object = None                                 # own top_p / top_k / win_size / tau_r (dict or partial) in a mixed-sampling grid; None: the LM's
 
 
 @dataclass
@@ -285,7 +286,7 @@ class HvxPipeline:
 
     @torch.inference_mode()
     def serve(self, source, lm_slots=16, acoustic_batch=None, acoustic_min_batch=1, max_out=None, max_prefix=None,
-              max_token_text_ratio=20, min_token_text_ratio=2, pace=None):
+              max_token_text_ratio=20, min_token_text_ratio=2, pace=None, mixed_sampling=False, win_cap=None):
         """The continuous engine over an open-ended SOURCE of utterances: `source.poll(block)` returns the next `Utterance`, or None when
         nothing is waiting (it is asked to block only while the decode grid is idle), and raises StopIteration when closed.  Generator over
         (utterance, waveform | exception, tokens) in completion order.
@@ -299,7 +300,9 @@ class HvxPipeline:
         fetched from the source and got no result is listed in `self.last_continuous['abandoned']`.  Source protocol: `poll(block)` as above and,
         optionally, `unpoll(utterance)` — an utterance fetched in the instant of a cancellation is handed back through it (the queue worker's
         sources implement it and re-serve the request); without `unpoll` it joins the abandoned list.
-        `pace` = (first, every_steps, more): admission pacing of the decode grid (see _DecodeEngine.run)."""
+        `pace` = (first, every_steps, more): admission pacing of the decode grid (see _DecodeEngine.run).
+        `mixed_sampling`: utterances may carry their own `sampling` and decode side by side with others' (HvxLLM.generate_stream; `win_cap` is
+        the longest repetition window the grid holds).  Off, an utterance that carries `sampling` comes back with an error."""
         acoustic_batch = acoustic_batch or self.acoustic_batch
         acoustic_min_batch = max(1, min(int(acoustic_min_batch), acoustic_batch))
         import queue
@@ -357,7 +360,7 @@ class HvxPipeline:
                 tag = n_seen[0]
                 n_seen[0] += 1
                 seen[tag] = u
-                return dict(text=u.text, prompt_text=u.prompt_text, prompt_speech_token=u.prompt_speech_token, seed=u.seed, tag=tag,
+                return dict(text=u.text, prompt_text=u.prompt_text, prompt_speech_token=u.prompt_speech_token, seed=u.seed, tag=tag, sampling=u.sampling,
                             max_token_text_ratio=max_token_text_ratio if u.max_token_text_ratio is None else u.max_token_text_ratio,
                             min_token_text_ratio=min_token_text_ratio if u.min_token_text_ratio is None else u.min_token_text_ratio)
 
@@ -375,7 +378,8 @@ class HvxPipeline:
                 torch.cuda.set_device(stream.device)               # the current device is per thread
                 with torch.inference_mode():
                     t0 = time.time()
-                    gen = self.llm.generate_stream(_Requests(), n_slots=lm_slots, max_out=max_out, max_prefix=max_prefix, pace=pace)
+                    gen = self.llm.generate_stream(_Requests(), n_slots=lm_slots, max_out=max_out, max_prefix=max_prefix, pace=pace,
+                                                   **(dict(mixed_sampling=True, win_cap=win_cap) if mixed_sampling else {}))
                     try:
                         for tag, toks in gen:
                             if not put((tag, toks)):

@@ -92,17 +92,38 @@ class _TaskSource:
     parameters become utterances as they arrive and join the decode grid while earlier ones are still in flight.  The first task that cannot
     join — a `load_pt`, other sampling parameters (llm.sampling / inference_head_num are per-model state, server/worker.py:57-65), an unknown
     type, the shutdown sentinel — closes the epoch: it is kept in `carry` and served after everything accepted before it has finished, so
-    arrival order around a hot swap is what the reference's one-by-one loop gives."""
+    arrival order around a hot swap is what the reference's one-by-one loop gives.
+    mixed_sampling: top_p / top_k / win_size / tau_r are per-sequence state of the decode grid (HvxLLM.generate_stream(mixed_sampling=True)), so
+    a task with other values joins the running epoch and its utterance carries them (`Utterance.sampling`; a task without extra_params
+    carries None and takes the epoch's).  What still closes the epoch: another inference_head_num (it sets the grid's row count), a window
+    that a ring of `win_cap` entries cannot hold (0 = whole history, or more than win_cap), a top_k outside [1, 64], and everything above."""
 
-    def __init__(self, mm, task_queue, result_dict, first, normalise, worker_id):
+    def __init__(self, mm, task_queue, result_dict, first, normalise, worker_id, mixed_sampling=False, win_cap=64):
         self.mm, self.q, self.results, self.normalise, self.worker_id = mm, task_queue, result_dict, normalise, worker_id
+        self.mixed, self.win_cap = bool(mixed_sampling), int(win_cap)
         self.key = _sampling_key(first)
+        # the head count the epoch's grid is built with: the first task's, or (a first task without extra_params) what the model holds
+        llm = (getattr(mm, 'models', None) or {}).get('llm')
+        self.head_num = self.key[4] if first.get('extra_params') else getattr(llm, 'inference_head_num', None)
         self.head = first
         self.carry = None
         self.stop = False
         self.closed = False
 
     POLL_SECONDS = 0.1
+
+    def _joins(self, t):
+        """does task t (tts / zero_shot, not segmented) belong to this epoch?"""
+        if not self.mixed:
+            return _sampling_key(t) == self.key
+        ep = t.get('extra_params')
+        if not ep:
+            return True                                # the epoch's defaults, whatever they are
+        try:
+            fits = 1 <= int(ep['win_size']) <= self.win_cap and 1 <= int(ep['top_k']) <= 64
+        except (KeyError, TypeError, ValueError):
+            return False                               # (an incomplete set: served on its own, where the one-by-one rules answer it)
+        return fits and ep.get('inference_head_num') is not None and ep.get('inference_head_num') == self.head_num
 
     def unpoll(self, u):
         """an utterance the engine fetched while it was being cancelled: its task opens the next epoch instead of failing with this one"""
@@ -134,6 +155,9 @@ class _TaskSource:
         u.speed = float((t.get('extra_params') or {}).get('speed', 1.0))
         if u.speed <= 0:
             raise ValueError('Invalid speed: %s' % u.speed)
+        if self.mixed and t.get('extra_params'):
+            ep = t['extra_params']
+            u.sampling = dict(top_p=ep['top_p'], top_k=ep['top_k'], win_size=ep['win_size'], tau_r=ep['tau_r'])
         u.tag = t
         return u
 
@@ -154,7 +178,7 @@ class _TaskSource:
             if t is None:
                 self.stop = self.closed = True
                 raise StopIteration
-            if t.get('task_type') not in ('tts', 'zero_shot') or _sampling_key(t) != self.key or _is_segmented(t, self.normalise):
+            if t.get('task_type') not in ('tts', 'zero_shot') or not self._joins(t) or _is_segmented(t, self.normalise):
                 self.carry, self.closed = t, True
                 raise StopIteration
             try:
@@ -164,13 +188,16 @@ class _TaskSource:
                 self.results[t['id']] = {'error': str(e)}
 
 
-def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_id, frontend_factory=None, lm_slots=None, acoustic_batch=4):
+def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_id, frontend_factory=None, lm_slots=None, acoustic_batch=4,
+                               mixed_sampling=False):
     """Same wire format as worker_process_tts, served by the continuous-batching engine (replaces the one-request-at-a-time
     loop of server/worker.py:54-102 and what server/router.py:144-156 feeds it): `tts` / `zero_shot` tasks join ONE decode grid as they arrive
     (HvxPipeline.serve -> HvxLLM.generate_stream: the LM weights are streamed once per step for every request in flight, a finished request's
     slot goes to the next waiting one), finished requests go to length-bucketed padded CFM solves and the vocoder beside the decode of the
     others, and every result is written to `result_dict` the moment its waveform is complete.  `load_pt` and a change of sampling parameters
-    are epoch boundaries (FIFO: see _TaskSource).  What bench.py measures is this path."""
+    are epoch boundaries (FIFO: see _TaskSource).  What bench.py measures is this path.
+    mixed_sampling=True: requests with different top_p / top_k / win_size / tau_r share the grid, each sampling with its own values; only
+    another inference_head_num, a window over 64 (or 0) and the non-synthesis tasks remain epoch boundaries."""
     os.environ['CUDA_VISIBLE_DEVICES'] = str(worker_id % num_workers_gpu)
     from .model_manager import HvxModelManager
     from .pipeline import HvxPipeline
@@ -179,11 +206,14 @@ def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_
     mm = HvxModelManager(frontend_factory=frontend_factory)
     mm.load_models(argparse.Namespace(config=os.getenv('TTS_CONFIG'), model_dir=os.getenv('TTS_MODEL_DIR'), bf16=_env_flag('TTS_BF_16'),
                                       fp16=_env_flag('TTS_FP_16'), cpu=_env_flag('TTS_CPU', False)))
-    serve_queue(mm, task_queue, result_dict, worker_id, lm_slots=lm_slots, acoustic_batch=acoustic_batch)
+    serve_queue(mm, task_queue, result_dict, worker_id, lm_slots=lm_slots, acoustic_batch=acoustic_batch, mixed_sampling=mixed_sampling)
 
 
-def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acoustic_batch=4, normalise=None):
-    """the loop of worker_process_tts_batched over an already loaded model manager (tests drive this directly)"""
+def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acoustic_batch=4, normalise=None, mixed_sampling=False, win_cap=64, token_log=None):
+    """the loop of worker_process_tts_batched over an already loaded model manager (tests drive this directly).  Returns its counters:
+    `epochs` (decode grids started) and `epoch_boundaries` (tasks that closed a running grid because they could not join it; the shutdown
+    sentinel is not one).  token_log: a dict that receives task id -> speech-token ids of every synthesised request."""
+    stats = dict(epochs=0, epoch_boundaries=0, mixed_sampling=bool(mixed_sampling))
     from .pipeline import HvxPipeline
     from .sampling import ras_sampling
     normalise = normalise or _text_normaliser()
@@ -209,14 +239,21 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
                 result = {'error': str(e)}
             result_dict[task['id']] = result
             continue
-        src = _TaskSource(mm, task_queue, result_dict, task, normalise, worker_id)
+        src = _TaskSource(mm, task_queue, result_dict, task, normalise, worker_id, mixed_sampling=mixed_sampling, win_cap=win_cap)
+        if mixed_sampling and not src._joins(task):
+            # a request no mixed grid can hold (window 0 or over win_cap): an epoch of its own on the scalar engine, as without the switch
+            src = _TaskSource(mm, task_queue, result_dict, task, normalise, worker_id)
         in_flight = {}
+        stats['epochs'] += 1
         try:
             apply_extra_params(mm, task, ras_sampling)
             pipe.llm = mm.models['llm']
-            for u, wav, toks in pipe.serve(_Tracked(src, in_flight), lm_slots=lm_slots, acoustic_batch=acoustic_batch, acoustic_min_batch=1):
+            kw = dict(mixed_sampling=True, win_cap=win_cap) if src.mixed else {}
+            for u, wav, toks in pipe.serve(_Tracked(src, in_flight), lm_slots=lm_slots, acoustic_batch=acoustic_batch, acoustic_min_batch=1, **kw):
                 t = u.tag
                 in_flight.pop(t['id'], None)
+                if token_log is not None and not isinstance(wav, BaseException):
+                    token_log[t['id']] = list(toks)
                 if isinstance(wav, BaseException):
                     logger.error('[TTS Worker-%d] Error: %s', worker_id, wav)
                     result_dict[t['id']] = {'error': str(wav)}
@@ -232,8 +269,11 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
             for tid in list(in_flight):
                 result_dict[tid] = {'error': str(e)}
         carry = src.carry
+        if carry is not None:
+            stats['epoch_boundaries'] += 1
         if src.stop:
             break
+    return stats
 
 
 class _Tracked:

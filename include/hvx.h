@@ -79,6 +79,18 @@ typedef struct {
     const int64_t* noise_limit;   /* optional [n_seq]: `noise` is then a ring addressed by absolute stream position % noise_len, valid below the limit */
 } hvx_sample_args;
 int hvx_ras_sample(const hvx_sample_args* a, hvx_stream s);
+/* Per-sequence sampling parameters: four device arrays of [n_seq] entries, all of them given.  The reference sets top_k / top_p / win_size /
+ * tau_r per REQUEST (server/worker.py:57-65); with this block every sequence of a launch — every slot of a decode grid — samples with its
+ * own values and the scalar fields of the argument struct are not read.  rep_thresh = ceil(win_size * tau_r), computed on the host in
+ * double.  The sampler clamps top_k to [1, 64] and reads each sequence's values once per launch. */
+typedef struct {
+    const int32_t* top_k;
+    const float*   top_p;
+    const int32_t* win_size;
+    const int32_t* rep_thresh;
+} hvx_seq_sampling;
+/* hvx_ras_sample with a sampling block; q == NULL is hvx_ras_sample */
+int hvx_ras_sample_seq(const hvx_sample_args* a, const hvx_seq_sampling* q, hvx_stream s);
 
 /* ---------------------------------------------------------------------------------------------------
  * Building-block operators (exported for the parity tests; the model entry points below are chains of these)
@@ -285,6 +297,11 @@ typedef struct {
     const int64_t* noise_limit;   /* [n_seq] absolute positions up to which the noise ring is filled (the caller tops it up while steps run) */
 } hvx_decode_args;
 int hvx_llm_decode_steps(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, int32_t n_steps);
+/* The same loop with per-sequence sampling parameters (q == NULL is hvx_llm_decode_steps).  The cached step graph is keyed on the sampling
+ * block too; its arrays sit at fixed addresses, so a replay reads whatever the last hvx_llm_decode_join_seq wrote.  With a block, a
+ * sequence's repetition ring is win_size[i] entries long (clamped to [1, win_cap]): slot = out_len % win_size[i], hist_len =
+ * min(out_len, win_size[i]) — the ring holds exactly the last min(win_size[i], out_len) tokens the sampler counts over, wrapped or not. */
+int hvx_llm_decode_steps_seq(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, const hvx_seq_sampling* q, int32_t n_steps);
 /* Continuous batching — the batching scheduler SURVEY.md §8(f) N1 asks for in place of the reference's one-request-at-a-time worker loop
  * (server/worker.py:54-102): between two hvx_llm_decode_steps calls on the same stream a new sequence takes over slot `slot` of the grid
  * described by `a` (a finished sequence's slot, or one that was never used).  The caller has prefilled all but the last prefix row into
@@ -293,6 +310,12 @@ int hvx_llm_decode_steps(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, int
  * limits, an empty repetition window, cursor 0, active. */
 int hvx_llm_decode_join(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, int32_t slot, int32_t first_tok, int32_t pos,
                         int32_t min_len, int32_t max_len);
+/* hvx_llm_decode_join plus the slot's four sampling values, written into the arrays of `q` by the same kernel that writes the rest of the
+ * slot's state (so they are ordered on the stream behind the blocks already enqueued, and a slot never samples with its predecessor's).
+ * Refused — -1, hvx_last_error, nothing launched — when top_k is outside [1, 64], top_p <= 0, win_size outside [1, a->win_cap] or
+ * rep_thresh < 0. */
+int hvx_llm_decode_join_seq(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, const hvx_seq_sampling* q, int32_t slot, int32_t first_tok,
+                            int32_t pos, int32_t min_len, int32_t max_len, int32_t top_k, float top_p, int32_t win_size, int32_t rep_thresh);
 /* debugging / parity: copy the post-final-norm hidden of the last rows of the previous forward (fp32 [n_seq][H]) */
 int hvx_llm_last_hidden(hvx_llm* h, hvx_stream s, int32_t n_seq, float* out);
 

@@ -3,7 +3,11 @@
 bench workload: N `tts` tasks of 512 text tokens pushed through a queue, HydraVox-CV3 bf16 LM + flow, fp32-contract vocoder, seeded random
 weights; a stand-in frontend turns the task text into token ids (the real text / audio frontends are outside this build).
 
-    python tools/bench_worker.py [--tasks 64] [--chars 512] [--lm-slots 64] [--acoustic-batch 4] [--one-by-one]
+    python tools/bench_worker.py [--tasks 64] [--chars 512] [--lm-slots 64] [--acoustic-batch 4] [--one-by-one] [--alternate-sampling] [--mixed-sampling]
+
+--alternate-sampling: the tasks carry `extra_params` that alternate between two sampling parameter sets (same inference_head_num) — the worst
+case for the worker's epochs: without --mixed-sampling every task closes the running decode grid.  --mixed-sampling serves the queue with
+serve_queue(mixed_sampling=True): the parameters are per-sequence state of the grid and the tasks share it.
 """
 import argparse
 import json
@@ -24,6 +28,8 @@ ap.add_argument('--chars', type=int, default=512)
 ap.add_argument('--lm-slots', type=int, default=64)
 ap.add_argument('--acoustic-batch', type=int, default=4)
 ap.add_argument('--one-by-one', action='store_true', help='the reference loop instead: worker_process_tts semantics, one task at a time')
+ap.add_argument('--alternate-sampling', action='store_true', help='tasks alternate between two sampling parameter sets (extra_params)')
+ap.add_argument('--mixed-sampling', action='store_true', help='serve_queue(mixed_sampling=True): requests with different sampling parameters share the grid')
 a = ap.parse_args()
 from flowmirror_hydravox_amd import cv3_config, weights as W  # noqa: E402
 from flowmirror_hydravox_amd.flow import HvxFlow  # noqa: E402
@@ -61,10 +67,17 @@ _serve = P.HvxPipeline.serve
 P.HvxPipeline.serve = lambda self, src, **kw: _serve(self, src, max_token_text_ratio=ratio, min_token_text_ratio=ratio, **kw)
 
 
+SETS = [dict(top_p=0.9, top_k=10, win_size=32, tau_r=0.2, inference_head_num=2), dict(top_p=0.8, top_k=25, win_size=10, tau_r=0.1, inference_head_num=2)]
+counters = {}
+
+
 def run(n, one_by_one):
     q, results = queue.Queue(), {}
     for i in range(n):
-        q.put(dict(id=i, task_type='tts', text=str(i), speaker_id='s', seed=i))
+        t = dict(id=i, task_type='tts', text=str(i), speaker_id='s', seed=i)
+        if a.alternate_sampling:
+            t['extra_params'] = dict(SETS[i % 2])
+        q.put(t)
     q.put(None)
     torch.cuda.synchronize()
     t0 = time.time()
@@ -75,11 +88,14 @@ def run(n, one_by_one):
             if t is None:
                 break
             llm.inference = lambda **kw: orig(seed=t['seed'], **dict(kw, max_token_text_ratio=ratio, min_token_text_ratio=ratio))
+            if 'extra_params' in t:
+                ep = t['extra_params']
+                llm.sampling = partial(ras_sampling, top_p=ep['top_p'], top_k=ep['top_k'], win_size=ep['win_size'], tau_r=ep['tau_r'])
             out = _synthesize(mm, mm.frontend.frontend_sft(t['text'], t['speaker_id']), 1.0, zero_shot=False)
             results[t['id']] = {'output_audio': out, 'duration': out.shape[-1] / 24000}
         llm.inference = orig
     else:
-        serve_queue(mm, q, results, lm_slots=a.lm_slots, acoustic_batch=a.acoustic_batch, normalise=lambda s: s)
+        counters.update(serve_queue(mm, q, results, lm_slots=a.lm_slots, acoustic_batch=a.acoustic_batch, normalise=lambda s: s, mixed_sampling=a.mixed_sampling) or {})
     torch.cuda.synchronize()
     dt = time.time() - t0
     assert len(results) == n and all('output_audio' in r for r in results.values()), [r for r in results.values() if 'error' in r][:2]
@@ -91,4 +107,5 @@ run(min(a.tasks, 4), a.one_by_one)                       # warm-up (graphs, work
 dt, audio = run(a.tasks, a.one_by_one)
 print(json.dumps({'path': 'worker_process_tts (one task at a time, reference loop)' if a.one_by_one else 'worker.serve_queue (continuous engine)', 'tasks': a.tasks,
                   'chars': a.chars, 'seconds': round(dt, 2), 'requests_per_s': round(a.tasks / dt, 3), 'speech_tokens_per_s': round(a.tasks * n_spk / dt, 1),
-                  'rtf': round(dt / audio, 6), 'lm_slots': a.lm_slots, 'acoustic_batch': a.acoustic_batch}))
+                  'rtf': round(dt / audio, 6), 'lm_slots': a.lm_slots, 'acoustic_batch': a.acoustic_batch, 'alternate_sampling': a.alternate_sampling,
+                  'mixed_sampling': a.mixed_sampling, 'epochs': counters.get('epochs'), 'epoch_boundaries': counters.get('epoch_boundaries')}))
