@@ -36,6 +36,11 @@ class SeqSampling(C.Structure):
     _fields_ = [('top_k', c_vp), ('top_p', c_vp), ('win_size', c_vp), ('rep_thresh', c_vp)]
 
 
+class SeqHeads(C.Structure):
+    """hvx_seq_heads: per-sequence head counts, one device array of [n_seq] int32"""
+    _fields_ = [('head_k', c_vp)]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [('dtype', c_i32), ('M', c_i32), ('N', c_i32), ('K', c_i32), ('batch', c_i32), ('groups', c_i32),
                 ('A', c_vp), ('a_bs', c_i64), ('lda', c_i32), ('a_gs', c_i32), ('rows_in', c_i32),
@@ -166,6 +171,7 @@ SYMBOLS = {
     'hvx_prof_read': (c_i32, [c_i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(C.c_double)]),
     'hvx_ras_sample': (c_i32, [C.POINTER(SampleArgs), c_vp]),
     'hvx_ras_sample_seq': (c_i32, [C.POINTER(SampleArgs), C.POINTER(SeqSampling), c_vp]),
+    'hvx_ras_sample_mixed': (c_i32, [C.POINTER(SampleArgs), C.POINTER(SeqSampling), C.POINTER(SeqHeads), c_vp]),
     'hvx_op_gemm': (c_i32, [C.POINTER(GemmArgs), c_vp]),
     'hvx_op_act_rows': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i64, c_i32, c_f32, c_vp, c_i64, c_i32, c_vp]),
     'hvx_op_attention': (c_i32, [C.POINTER(AttnArgs), c_vp]),
@@ -186,6 +192,9 @@ SYMBOLS = {
     'hvx_llm_decode_steps_seq': (c_i32, [c_vp, c_vp, C.POINTER(DecodeArgs), C.POINTER(SeqSampling), c_i32]),
     'hvx_llm_decode_join_seq': (c_i32, [c_vp, c_vp, C.POINTER(DecodeArgs), C.POINTER(SeqSampling), c_i32, c_i32, c_i32, c_i32, c_i32,
                                         c_i32, c_f32, c_i32, c_i32]),
+    'hvx_llm_decode_steps_mixed': (c_i32, [c_vp, c_vp, C.POINTER(DecodeArgs), C.POINTER(SeqSampling), C.POINTER(SeqHeads), c_i32, c_i32]),
+    'hvx_llm_decode_join_mixed': (c_i32, [c_vp, c_vp, C.POINTER(DecodeArgs), C.POINTER(SeqSampling), C.POINTER(SeqHeads), c_i32, c_i32, c_i32, c_i32, c_i32,
+                                          c_i32, c_f32, c_i32, c_i32, c_i32]),
     'hvx_llm_use_graph': (c_i32, [c_vp, c_i32]),
     'hvx_llm_set_head_mlp_fp8': (c_i32, [c_vp, c_vp, c_vp]),
     'hvx_llm_last_hidden': (c_i32, [c_vp, c_vp, c_i32, c_vp]),
@@ -244,7 +253,8 @@ SYMBOLS = {
 # the narrow residual projection behind it).  The one exception to "bumped whenever a symbol is added": hvx_op_resample_sinc (the prompt resampler) joined at version
 # 7 — no struct changed and no existing symbol changed meaning, and a library of version 7 built before it fails in load() below on the missing symbol, with the
 # rebuild command, exactly as a version mismatch would.  The per-sequence sampling entry points (hvx_ras_sample_seq, hvx_llm_decode_steps_seq,
-# hvx_llm_decode_join_seq and their hvx_seq_sampling block) joined the same way: additive, no existing struct or symbol touched.
+# hvx_llm_decode_join_seq and their hvx_seq_sampling block) joined the same way: additive, no existing struct or symbol touched; so did the
+# per-sequence head counts (hvx_ras_sample_mixed, hvx_llm_decode_steps_mixed, hvx_llm_decode_join_mixed and hvx_seq_heads).
 HVX_ABI_VERSION = 7
 
 _lib = None

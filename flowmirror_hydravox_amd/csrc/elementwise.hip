@@ -254,10 +254,11 @@ int launch_embed2(const void* speech, const void* text, int dtype, const int* to
 }
 
 // ---- log_softmax over V (llm_multi_head_v3.py:888) ------------------------------------------------------
-__global__ __launch_bounds__(256) void log_softmax_kernel(float* x, int ld, int V) {
+__global__ __launch_bounds__(256) void log_softmax_kernel(float* x, int ld, int V, int grp, int grp_stride) {
     extern __shared__ __attribute__((aligned(16))) float row[];      // the row is read from global memory once
     __shared__ float red[4];
-    float* xr = x + (long long)blockIdx.x * ld;
+    const int b = blockIdx.x;
+    float* xr = x + (long long)(grp == grp_stride ? b : (b / grp) * grp_stride + b % grp) * ld;
     float mx = -INFINITY;
     for (int base = 0; base < V; base += 256 * 8) {
         float t[8];
@@ -280,9 +281,10 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(float* x, int ld, int 
     const float lse = mx + logf(sum);
     for (int c = threadIdx.x; c < V; c += 256) xr[c] = row[c] - lse;
 }
-int launch_log_softmax(float* x, int ld, int rows, int V, hipStream_t s) {
+int launch_log_softmax(float* x, int ld, int rows, int V, hipStream_t s, int grp, int grp_stride) {
     if (rows <= 0) return 0;
-    hipLaunchKernelGGL(log_softmax_kernel, dim3(rows), dim3(256), (size_t)V * 4, s, x, ld, V);
+    if (grp < 1 || grp > grp_stride) return set_error("log_softmax: group %d of %d rows", grp, grp_stride), -1;
+    hipLaunchKernelGGL(log_softmax_kernel, dim3(rows), dim3(256), (size_t)V * 4, s, x, ld, V, grp, grp_stride);
     return hipGetLastError() == hipSuccess ? 0 : (set_error("log_softmax launch failed"), -1);
 }
 

@@ -211,8 +211,11 @@ int hvx_prof_read(int32_t kind, double* sampled_ms, double* sampled_work, int64_
     return 0;
 }
 
-int hvx_ras_sample_seq(const hvx_sample_args* a, const hvx_seq_sampling* q, hvx_stream s) {
+int hvx_ras_sample_seq(const hvx_sample_args* a, const hvx_seq_sampling* q, hvx_stream s) { return hvx_ras_sample_mixed(a, q, nullptr, s); }
+
+int hvx_ras_sample_mixed(const hvx_sample_args* a, const hvx_seq_sampling* q, const hvx_seq_heads* heads, hvx_stream s) {
     if (!a) return set_error("hvx_ras_sample: null args"), -1;
+    if (heads && !heads->head_k) return set_error("hvx_ras_sample_mixed: the heads block needs its array"), -1;
     if (q && (!q->top_k || !q->top_p || !q->win_size || !q->rep_thresh)) return set_error("hvx_ras_sample_seq: the sampling block needs all four arrays"), -1;
     SampleArgs k;
     memset(&k, 0, sizeof(k));
@@ -224,6 +227,7 @@ int hvx_ras_sample_seq(const hvx_sample_args* a, const hvx_seq_sampling* q, hvx_
     k.noise = a->noise; k.noise_ss = a->noise_seq_stride; k.noise_len = a->noise_len; k.noise_limit = (const long long*)a->noise_limit;
     k.cursor = (long long*)a->cursor; k.out_ids = a->out_ids; k.max_trials = a->max_trials;
     if (q) { k.seq_top_k = q->top_k; k.seq_top_p = q->top_p; k.seq_win = q->win_size; k.seq_thresh = q->rep_thresh; }
+    if (heads) k.seq_heads = heads->head_k;
     return launch_ras_sample(k, (hipStream_t)s);
 }
 

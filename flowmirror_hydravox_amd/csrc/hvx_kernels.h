@@ -200,7 +200,8 @@ int launch_embed(const void* table, int table_dtype, const int* tok, float* x, i
 int launch_embed2(const void* speech, const void* text, int dtype, const int* tok, float* x, int ldx, void* x_copy, int rows, int H, hipStream_t s,
                   int copy_frag = 0);
 // logits -> log_softmax (fp32, in place) over V columns, one block per row
-int launch_log_softmax(float* x, int ld, int rows, int V, hipStream_t s);
+// row b of the launch is row (b / grp) * grp_stride + b % grp of x: the first grp of every grp_stride rows (the live heads of a [S][K][V] block)
+int launch_log_softmax(float* x, int ld, int rows, int V, hipStream_t s, int grp = 1, int grp_stride = 1);
 // DiT: y = dtype( LN(x; eps, no affine) * (1 + scale[b]) + shift[b] ); x f32 [B][T][D]; shift/scale f32 [B][.] with stride mod_bs
 int launch_layernorm_mod(const void* x, int x_f16, const float* shift, const float* scale, long long mod_bs, float eps, void* y, int dtype,
                          int B, int T, int D, hipStream_t s);
@@ -256,6 +257,9 @@ struct SampleArgs {
     // optional per-sequence sampling parameters, [n_seq] each, all four or none (none: the scalars above serve every sequence).  The kernel
     // clamps seq_top_k to [1, MAX_CAND] itself: a device array cannot be validated at launch.
     const int* seq_top_k; const float* seq_top_p; const int* seq_win; const int* seq_thresh;
+    // optional per-sequence head count, [n_seq] (NULL: head_k for everybody).  Sequence s samples heads j < clamp(seq_heads[s], 1, head_k) only; the
+    // others consume no noise, their log-prob rows are never read and their out_ids entries are -3 ("no head").
+    const int* seq_heads;
 };
 int launch_ras_sample(const SampleArgs& a, hipStream_t s);
 
@@ -271,6 +275,9 @@ struct AdvanceArgs {
     // optional per-sequence sampling parameters (SampleArgs: seq_*).  With them a sequence's repetition ring is seq_win[i] entries long
     // (clamped to [1, win_cap]) instead of win_cap: the ring then holds exactly the window the sampler counts over, wrapped or not.
     int* seq_top_k; float* seq_top_p; int* seq_win; int* seq_thresh;
+    // optional per-sequence head count (SampleArgs: seq_heads): a sequence accepts at most clamp(seq_heads[i], 1, head_k) ids per step; the row
+    // stride of ids / tok stays head_k
+    int* seq_heads;
 };
 // the four per-sequence sampling values a joining sequence brings along (written by the join kernel beside the rest of the slot's state)
 struct SeqSampling {
@@ -278,7 +285,7 @@ struct SeqSampling {
 };
 int launch_decode_advance(const AdvanceArgs& a, hipStream_t s);
 int launch_decode_join(const AdvanceArgs& a, long long* cursor, int slot, int first_tok, int pos, int min_len, int max_len, hipStream_t s,
-                       const SeqSampling* q = nullptr);
+                       const SeqSampling* q = nullptr, int heads = 0);      // heads > 0: the slot's head count, written to a.seq_heads[slot]
 
 // ------------------------------------------------------------------------------------------------
 // HiFT source / STFT / iSTFT

@@ -42,6 +42,8 @@ struct hvx_llm {
     struct StepGraph {
         hvx_decode_args a;
         hvx_seq_sampling q;                  // (all NULL: the scalar form)
+        const int32_t* heads;                // per-sequence head counts (NULL: head_k for everybody)
+        int heads_live;                      // heads the forward computes (a.head_k without a heads block)
         hipStream_t s;
         hipGraphExec_t ex;
     };
@@ -222,8 +224,9 @@ static int resid_wide(hvx_llm* h, SkinnyArgs g, const void* w_frag, void* xcopy,
     return launch_reduce_rmsnorm(r, s);
 }
 
+// heads_live (0: head_k): only the first heads_live of the head_k heads are computed; logp keeps its [n_seq][head_k][vocab] layout
 static int forward_impl(hvx_llm* h, hipStream_t s, int32_t n_seq, int32_t kn, const int32_t* tok, const int32_t* ctrl, int32_t head_k,
-                        float* logp);
+                        float* logp, int32_t heads_live = 0);
 
 // The decode step is ~200 short launches; replaying them as one hipGraph removes the per-launch host cost.  Every kernel
 // argument is a fixed device address (control arrays, KV cache, workspace) and every data-dependent quantity (context
@@ -264,8 +267,8 @@ static void set_seq(AdvanceArgs& aa, const hvx_seq_sampling& q) {
     aa.seq_win = const_cast<int*>(q.win_size); aa.seq_thresh = const_cast<int*>(q.rep_thresh);
 }
 
-static int decode_step_impl(hvx_llm* h, hipStream_t s, const hvx_decode_args& a, const hvx_seq_sampling& q) {
-    if (forward_impl(h, s, a.n_seq, a.head_k, a.tok, a.ctrl, a.head_k, a.logp)) return -1;
+static int decode_step_impl(hvx_llm* h, hipStream_t s, const hvx_decode_args& a, const hvx_seq_sampling& q, const int32_t* heads, int heads_live) {
+    if (forward_impl(h, s, a.n_seq, a.head_k, a.tok, a.ctrl, a.head_k, a.logp, heads_live)) return -1;
     SampleArgs sa;
     memset(&sa, 0, sizeof(sa));
     sa.n_seq = a.n_seq; sa.head_k = a.head_k; sa.V = h->c.vocab; sa.Vs = h->c.speech_tokens;
@@ -275,6 +278,7 @@ static int decode_step_impl(hvx_llm* h, hipStream_t s, const hvx_decode_args& a,
     sa.noise = a.noise; sa.noise_ss = a.noise_seq_stride; sa.noise_len = a.noise_len; sa.noise_limit = (const long long*)a.noise_limit; sa.cursor = (long long*)a.cursor;
     sa.out_ids = a.ids; sa.max_trials = a.max_trials;
     sa.seq_top_k = q.top_k; sa.seq_top_p = q.top_p; sa.seq_win = q.win_size; sa.seq_thresh = q.rep_thresh;
+    sa.seq_heads = heads;
     if (launch_ras_sample(sa, s)) return -1;
     AdvanceArgs aa;
     memset(&aa, 0, sizeof(aa));
@@ -282,6 +286,7 @@ static int decode_step_impl(hvx_llm* h, hipStream_t s, const hvx_decode_args& a,
     aa.ids = a.ids; aa.tok = a.tok; aa.ctrl = a.ctrl; aa.hist = a.hist; aa.hist_len = a.hist_len; aa.min_adj = a.min_adj; aa.active = a.active;
     aa.seq_state = a.seq_state; aa.out_tokens = a.out_tokens;
     set_seq(aa, q);
+    aa.seq_heads = const_cast<int*>(heads);
     return launch_decode_advance(aa, s);
 }
 
@@ -290,6 +295,11 @@ int hvx_llm_decode_steps(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a
 }
 
 int hvx_llm_decode_steps_seq(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, const hvx_seq_sampling* qp, int32_t n_steps) {
+    return hvx_llm_decode_steps_mixed(h, stream, a, qp, nullptr, a ? a->head_k : 0, n_steps);
+}
+
+int hvx_llm_decode_steps_mixed(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, const hvx_seq_sampling* qp, const hvx_seq_heads* hp,
+                               int32_t heads_live, int32_t n_steps) {
     if (!h || !h->ws || !a) return set_error("hvx_llm_decode_steps: handle not bound / null argument"), -1;
     hvx_seq_sampling q;
     memset(&q, 0, sizeof(q));
@@ -300,19 +310,27 @@ int hvx_llm_decode_steps_seq(hvx_llm* h, hvx_stream stream, const hvx_decode_arg
     if (a->n_seq < 1 || a->head_k < 1 || a->head_k > 8 || a->win_cap < 1 || a->max_out < 1 || !a->tok || !a->ctrl || !a->hist || !a->hist_len ||
         !a->min_adj || !a->active || !a->seq_state || !a->out_tokens || !a->ids || !a->logp || !a->noise || !a->cursor)
         return set_error("hvx_llm_decode_steps: bad argument block"), -1;
+    const int32_t* heads = nullptr;
+    if (hp) {
+        if (!hp->head_k) return set_error("hvx_llm_decode_steps_mixed: the heads block needs its array"), -1;
+        heads = hp->head_k;
+    }
+    // without per-sequence counts every sequence samples all head_k heads: all of them must be computed
+    if (heads_live < 1 || heads_live > a->head_k || (!heads && heads_live != a->head_k))
+        return set_error("hvx_llm_decode_steps_mixed: heads_live=%d outside [1,head_k=%d]%s", heads_live, a->head_k, heads ? "" : " (no heads block: it must be head_k)"), -1;
     hipStream_t s = (hipStream_t)stream;
     if (!h->use_graph || prof_enabled() || s == nullptr) {
         for (int i = 0; i < n_steps; ++i)
-            if (decode_step_impl(h, s, *a, q)) return -1;
+            if (decode_step_impl(h, s, *a, q, heads, heads_live)) return -1;
         return 0;
     }
     hipGraphExec_t ex = nullptr;
     for (auto& g : h->step_graphs)
-        if (g.s == s && memcmp(&g.a, a, sizeof(*a)) == 0 && memcmp(&g.q, &q, sizeof(q)) == 0) ex = g.ex;
+        if (g.s == s && memcmp(&g.a, a, sizeof(*a)) == 0 && memcmp(&g.q, &q, sizeof(q)) == 0 && g.heads == heads && g.heads_live == heads_live) ex = g.ex;
     if (!ex) {
         hipGraph_t g = nullptr;
         if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return set_error("hvx_llm_decode_steps: begin capture failed"), -1;
-        const int rc = decode_step_impl(h, s, *a, q);
+        const int rc = decode_step_impl(h, s, *a, q, heads, heads_live);
         const hipError_t e = hipStreamEndCapture(s, &g);
         if (rc != 0 || e != hipSuccess || !g) {
             if (g) hipGraphDestroy(g);
@@ -331,6 +349,8 @@ int hvx_llm_decode_steps_seq(hvx_llm* h, hvx_stream stream, const hvx_decode_arg
         hvx_llm::StepGraph sg;
         memcpy(&sg.a, a, sizeof(*a));                         // (byte copy: padding is compared too, callers pass a zeroed block)
         memcpy(&sg.q, &q, sizeof(q));
+        sg.heads = heads;
+        sg.heads_live = heads_live;
         sg.s = s;
         sg.ex = ex;
         h->step_graphs.push_back(sg);
@@ -341,7 +361,7 @@ int hvx_llm_decode_steps_seq(hvx_llm* h, hvx_stream stream, const hvx_decode_arg
 }
 
 static int decode_join_impl(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, const hvx_seq_sampling* q, const SeqSampling* v, int32_t slot,
-                            int32_t first_tok, int32_t pos, int32_t min_len, int32_t max_len) {
+                            int32_t first_tok, int32_t pos, int32_t min_len, int32_t max_len, const int32_t* heads = nullptr, int32_t head_k = 0) {
     if (!h || !h->ws || !a) return set_error("hvx_llm_decode_join: handle not bound / null argument"), -1;
     if (slot < 0 || slot >= a->n_seq || slot >= h->n_slots || pos < 0 || pos + 1 > h->max_ctx || !a->cursor)
         return set_error("hvx_llm_decode_join: slot %d / position %d outside the bound grid", slot, pos), -1;
@@ -351,7 +371,8 @@ static int decode_join_impl(hvx_llm* h, hvx_stream stream, const hvx_decode_args
     aa.ids = a->ids; aa.tok = a->tok; aa.ctrl = a->ctrl; aa.hist = a->hist; aa.hist_len = a->hist_len; aa.min_adj = a->min_adj; aa.active = a->active;
     aa.seq_state = a->seq_state; aa.out_tokens = a->out_tokens;
     if (q) set_seq(aa, *q);
-    return launch_decode_join(aa, (long long*)a->cursor, slot, first_tok, pos, min_len, max_len, (hipStream_t)stream, v);
+    aa.seq_heads = const_cast<int*>(heads);
+    return launch_decode_join(aa, (long long*)a->cursor, slot, first_tok, pos, min_len, max_len, (hipStream_t)stream, v, heads ? head_k : 0);
 }
 
 int hvx_llm_decode_join(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, int32_t slot, int32_t first_tok, int32_t pos,
@@ -361,15 +382,29 @@ int hvx_llm_decode_join(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a,
 
 int hvx_llm_decode_join_seq(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, const hvx_seq_sampling* q, int32_t slot, int32_t first_tok,
                             int32_t pos, int32_t min_len, int32_t max_len, int32_t top_k, float top_p, int32_t win_size, int32_t rep_thresh) {
-    if (!a || !q || !q->top_k || !q->top_p || !q->win_size || !q->rep_thresh)
+    if (!q) return set_error("hvx_llm_decode_join_seq: null argument / the sampling block needs all four arrays"), -1;
+    return hvx_llm_decode_join_mixed(h, stream, a, q, nullptr, slot, first_tok, pos, min_len, max_len, top_k, top_p, win_size, rep_thresh, 0);
+}
+
+int hvx_llm_decode_join_mixed(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, const hvx_seq_sampling* q, const hvx_seq_heads* hp, int32_t slot,
+                              int32_t first_tok, int32_t pos, int32_t min_len, int32_t max_len, int32_t top_k, float top_p, int32_t win_size,
+                              int32_t rep_thresh, int32_t head_k) {
+    if (!a) return set_error("hvx_llm_decode_join_mixed: null argument"), -1;
+    // everything is refused here, before anything is enqueued: the kernels can only clamp what they find in the arrays
+    if (hp) {
+        if (!hp->head_k) return set_error("hvx_llm_decode_join_mixed: the heads block needs its array"), -1;
+        if (head_k < 1 || head_k > a->head_k) return set_error("hvx_llm_decode_join_mixed: head count %d outside [1,head_k=%d]", head_k, a->head_k), -1;
+    }
+    const int32_t* heads = hp ? hp->head_k : nullptr;
+    if (!q) return decode_join_impl(h, stream, a, nullptr, nullptr, slot, first_tok, pos, min_len, max_len, heads, head_k);
+    if (!q->top_k || !q->top_p || !q->win_size || !q->rep_thresh)
         return set_error("hvx_llm_decode_join_seq: null argument / the sampling block needs all four arrays"), -1;
-    // refused here, before anything is enqueued: the kernels can only clamp what they find in the arrays
     if (top_k < 1 || top_k > 64) return set_error("hvx_llm_decode_join_seq: top_k=%d outside [1,64]", top_k), -1;
     if (!(top_p > 0.0f)) return set_error("hvx_llm_decode_join_seq: top_p=%g must be positive", (double)top_p), -1;
     if (win_size < 1 || win_size > a->win_cap) return set_error("hvx_llm_decode_join_seq: win_size=%d outside [1,win_cap=%d]", win_size, a->win_cap), -1;
     if (rep_thresh < 0) return set_error("hvx_llm_decode_join_seq: rep_thresh=%d is negative", rep_thresh), -1;
     const SeqSampling v{top_k, top_p, win_size, rep_thresh};
-    return decode_join_impl(h, stream, a, q, &v, slot, first_tok, pos, min_len, max_len);
+    return decode_join_impl(h, stream, a, q, &v, slot, first_tok, pos, min_len, max_len, heads, head_k);
 }
 
 int hvx_llm_use_graph(hvx_llm* h, int32_t enable) {
@@ -390,11 +425,13 @@ int hvx_llm_set_head_mlp_fp8(hvx_llm* h, const void* codes, const float* scales)
 }
 
 static int forward_impl(hvx_llm* h, hipStream_t s, int32_t n_seq, int32_t kn, const int32_t* tok, const int32_t* ctrl, int32_t head_k,
-                        float* logp) {
+                        float* logp, int32_t heads_live) {
     const hvx_llm_config& c = h->c;
     const int R = n_seq * kn;
     if (n_seq < 1 || kn < 1 || n_seq > h->max_seq || R > h->max_rows) return set_error("hvx_llm_forward: grid %dx%d exceeds the bound workspace", n_seq, kn), -1;
     if (head_k > c.head_num) return set_error("hvx_llm_forward: head_k=%d > head_num=%d", head_k, c.head_num), -1;
+    if (heads_live <= 0) heads_live = head_k;
+    if (heads_live > head_k) return set_error("hvx_llm_forward: heads_live=%d > head_k=%d", heads_live, head_k), -1;
     const int H = c.hidden, Q = c.q_heads * 64, G = c.q_heads / c.kv_heads;
     const int dt = c.dtype;
     const size_t es = dtype_size(dt);
@@ -518,7 +555,9 @@ static int forward_impl(hvx_llm* h, hipStream_t s, int32_t n_seq, int32_t kn, co
     // ---- last rows -> final RMSNorm (hidden_states[-1], llm_multi_head_v3.py:248-260, 886) ---------------------
     const int S = n_seq;
     const void* const* mw = w + 6 + 9 * c.layers;
-    const int A = c.mtp_attn_dim, I = c.mtp_inter, K = head_k;
+    // K: the heads that are computed (launch geometry nz = K: the weights of the others are not streamed); the [S][head_k][vocab] layout of the
+    // log-probs keeps head_k as its row stride, rows of heads >= K are left as they are
+    const int A = c.mtp_attn_dim, I = c.mtp_inter, K = heads_live;
     // ---- K MTP heads, batched over blockIdx.z; their residual copies and input norms come out of the same launch as the final norm ---
     if (launch_heads_prologue(h->x, H, d_last, (const float*)w[2], c.rms_eps, (const float*)mw[0], c.mtp_rms_eps, K, S, H, h->ylast, h->hx, h->ha, dt, s))
         return -1;
@@ -582,14 +621,14 @@ static int forward_impl(hvx_llm* h, hipStream_t s, int32_t n_seq, int32_t kn, co
     // straight into the caller's [S][K][vocab] buffer when there is one (the 16-row padding of the decoder is not stored)
     float* dst = logp ? logp : h->logits;
     const int ld = logp ? c.vocab : c.vocab_pad;
-    g.split_k = 1; g.nz = K; g.epi = SK_STORE; g.out = dst; g.out_f32 = 1; g.ldo = K * ld; g.out_zs = ld; g.n_valid = c.vocab;
+    g.split_k = 1; g.nz = K; g.epi = SK_STORE; g.out = dst; g.out_f32 = 1; g.ldo = head_k * ld; g.out_zs = ld; g.n_valid = c.vocab;
     if (dec_out) {
         g.a_frag = 1;
         const int rc = launch_dec_gemm(g, s);
         if (rc < 0) return -1;
         if (rc == 0) return set_error("hvx_llm_forward: output projection shape left the decode form"), -1;
     } else if (launch_skinny(g, s)) return -1;
-    if (launch_log_softmax(dst, ld, S * K, c.vocab, s)) return -1;
+    if (launch_log_softmax(dst, ld, S * K, c.vocab, s, K, head_k)) return -1;
     return 0;
 }
 

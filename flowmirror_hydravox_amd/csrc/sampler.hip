@@ -115,6 +115,9 @@ __global__ __launch_bounds__(256) void ras_sample_kernel(SampleArgs a) {
         top_k = min(max(top_k, 1), MAX_CAND);                // (the scalar is validated by launch_ras_sample; an array cannot be)
         win_size = max(win_size, 0);
     }
+    // The head count of this sequence, read once the same way: the head loop below runs __syncthreads under it.
+    int k_s = a.head_k;
+    if (a.seq_heads) k_s = min(max(__builtin_amdgcn_readfirstlane(a.seq_heads[s]), 1), a.head_k);
     const int win = (win_size == 0) ? hist_len : min(win_size, hist_len);
     bool overflow = false;
     // Everything the trial loops will touch is requested up front, beside the first head's logits: the repetition window (shared by
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(256) void ras_sample_kernel(SampleArgs a) {
     if (tid < HW && tid < win) s_hist[tid] = hist[hist_len - win + tid];
     auto noise_at = [&](long long i) -> float { return (i - cursor0) < NW ? s_noise[i - cursor0] : noise[i % cap]; };
 
-    for (int j = 0; j < a.head_k && !overflow; ++j) {
+    for (int j = 0; j < k_s && !overflow; ++j) {
         const float* lp = a.logp + (long long)s * a.logp_ss + (long long)j * a.logp_hs;
         // ---- softmax(logp) (common.py:149 / :165): 32 independent loads per thread, then registers only ------------
         float pv[VPT];
@@ -251,8 +254,10 @@ __global__ __launch_bounds__(256) void ras_sample_kernel(SampleArgs a) {
     }
     if (overflow) {
         if (tid < a.head_k) a.out_ids[(long long)s * a.head_k + tid] = -2;
-    } else if (tid == 0) {
-        a.cursor[s] = cursor;
+    } else {
+        // heads this sequence does not run: no noise consumed, no log-prob row read, -3 = "no head"
+        if (tid >= k_s && tid < a.head_k) a.out_ids[(long long)s * a.head_k + tid] = -3;
+        if (tid == 0) a.cursor[s] = cursor;
     }
 }
 
@@ -297,6 +302,8 @@ __global__ void decode_advance_kernel(AdvanceArgs a) {
     int n_next = 0;
     // ring length of this sequence: the engine-wide capacity, or the sequence's own window (see AdvanceArgs)
     const int ring = a.seq_win ? min(max(a.seq_win[i], 1), a.win_cap) : a.win_cap;
+    // heads of this sequence: at most that many ids are accepted per step (entries beyond them hold -3, see SampleArgs)
+    const int k_s = a.seq_heads ? min(max(a.seq_heads[i], 1), K) : K;
     if (!done && a.ids[i * K] == -2) {
         // the sampler ran out of pre-generated noise for this sequence (all K ids are -2, its cursor is untouched): the step is void.
         // Nothing advances — the same rows are fed again (rewriting the same KV entries) until the host has refilled the window.
@@ -306,7 +313,7 @@ __global__ void decode_advance_kernel(AdvanceArgs a) {
     if (!done) {
         st[6] = 0;                                           // (a stall flag from an earlier void step is history once a step counts)
         pos += a.ctrl[2 * a.n_seq + i];                      // rows fed by the step that just ran
-        for (int j = 0; j < K; ++j) {
+        for (int j = 0; j < k_s; ++j) {
             const int t = a.ids[i * K + j];
             if (t < 0) {                                     // -1: max_trials exhausted (the reference raises RuntimeError)
                 st[6] = 1;
@@ -348,8 +355,10 @@ __global__ void decode_advance_kernel(AdvanceArgs a) {
 
 // A new sequence takes over slot i of a running decode grid (continuous batching): what the host-side set-up of a batch writes for
 // every sequence, for one slot, ordered on the stream between two steps.  Its prefix but the last row is already in the slot's KV cache.
-__global__ void decode_join_kernel(AdvanceArgs a, long long* cursor, int i, int first_tok, int pos, int min_len, int max_len, int has_q, SeqSampling q) {
+__global__ void decode_join_kernel(AdvanceArgs a, long long* cursor, int i, int first_tok, int pos, int min_len, int max_len, int has_q, SeqSampling q,
+                                   int heads) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (heads > 0) a.seq_heads[i] = heads;
     if (has_q) {                                             // the slot's own sampling parameters: its predecessor's are history from here on
         a.seq_top_k[i] = q.top_k;
         a.seq_top_p[i] = q.top_p;
@@ -373,9 +382,12 @@ __global__ void decode_join_kernel(AdvanceArgs a, long long* cursor, int i, int 
 }
 
 int launch_decode_join(const AdvanceArgs& a, long long* cursor, int slot, int first_tok, int pos, int min_len, int max_len, hipStream_t s,
-                       const SeqSampling* q) {
+                       const SeqSampling* q, int heads) {
+    if (heads > 0 && !a.seq_heads) return set_error("decode_join: a head count without the seq_heads array"), -1;
+    if (heads > a.head_k) return set_error("decode_join: head count %d exceeds the grid's %d", heads, a.head_k), -1;
     if (q && (!a.seq_top_k || !a.seq_top_p || !a.seq_win || !a.seq_thresh)) return set_error("decode_join: per-sequence values without the four arrays"), -1;
-    hipLaunchKernelGGL(decode_join_kernel, dim3(1), dim3(64), 0, s, a, cursor, slot, first_tok, pos, min_len, max_len, q ? 1 : 0, q ? *q : SeqSampling{0, 0.0f, 0, 0});
+    hipLaunchKernelGGL(decode_join_kernel, dim3(1), dim3(64), 0, s, a, cursor, slot, first_tok, pos, min_len, max_len, q ? 1 : 0, q ? *q : SeqSampling{0, 0.0f, 0, 0},
+                       heads > 0 ? heads : 0);
     return hipGetLastError() == hipSuccess ? 0 : (set_error("decode_join launch failed"), -1);
 }
 

@@ -33,6 +33,12 @@ def _rope_tables(max_pos, head_dim, theta):
 
 
 
+def effective_heads(inference_head_num, head_num):
+    """heads a request decodes with: min(inference_head_num, head_num), <= 0 -> 1 (llm_multi_head_v3.py:867-869)"""
+    k = int(min(inference_head_num, head_num))
+    return 1 if k <= 0 else k
+
+
 def _fresh_seed():
     """a sampler seed for a request that came without one, drawn from (and advancing) torch's global CPU generator"""
     return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
@@ -51,6 +57,8 @@ class _Request:
         self.sp = None                    # own sampling parameters (a mixed-sampling grid): normalised dict, None = the engine's defaults
         self.thr = None                   # rep_threshold(win_size, tau_r) of those
         self.sp_error = None              # what was wrong with the parameters the request came with
+        self.heads = None                 # own inference_head_num (a mixed-heads grid), as the request gave it; None = the LM's
+        self.k = None                     # heads the request decodes with, set when it joins a mixed-heads grid
 
     def set_sampling(self, sampling):
         """the request's own top_p / top_k / win_size / tau_r, in any form sampling_params accepts; a bad set is kept as the request's error"""
@@ -321,7 +329,8 @@ class HvxLLM:
         self.last_stats = eng.stats
 
     @torch.inference_mode()
-    def generate_stream(self, requests, n_slots=None, max_out=None, max_prefix=None, pace=None, mixed_sampling=False, win_cap=None):
+    def generate_stream(self, requests, n_slots=None, max_out=None, max_prefix=None, pace=None, mixed_sampling=False, win_cap=None,
+                        mixed_heads=False, head_cap=None):
         """Continuous batching (replaces the one-request-at-a-time loop of server/worker.py:54-102): `requests` is an
         iterable of dicts (text, prompt_text, prompt_speech_token, seed, max_token_text_ratio, min_token_text_ratio, tag).  Up to `n_slots`
         sequences share one decode grid — the weights are streamed once per step for all of them — and the slot of a finished sequence is
@@ -331,7 +340,11 @@ class HvxLLM:
         top_p / top_k / win_size / tau_r, as `llm.sampling` takes them; without it the request samples with `llm.sampling`), and requests with
         different parameters decode side by side, each exactly as if it were served alone with its parameters on `llm.sampling`.  `win_cap`
         (default 64) is the longest repetition window such a grid holds; a request with a longer one, or with win_size 0 (whole history),
-        comes back with its error."""
+        comes back with its error.
+        mixed_heads: the head count is per-sequence state of the grid as well — a request dict may carry `inference_head_num` (effective count
+        min(n, head_num), <= 0 -> 1, as the reference; without the key the request takes `llm.inference_head_num`).  The grid is built with
+        `head_cap` rows per sequence (default: the model's head_num); every step computes only as many MTP heads as the widest request in
+        flight uses.  A count above `head_cap` comes back as that request's error.  Independent of mixed_sampling; both may be on."""
         n_slots = n_slots or self.max_batch
 
         def to_req(d):
@@ -343,6 +356,8 @@ class HvxLLM:
             r.tag = d.get('tag')
             if d.get('sampling') is not None:
                 r.set_sampling(d['sampling'])
+            if d.get('inference_head_num') is not None:
+                r.heads = int(d['inference_head_num'])
             return r
         if hasattr(requests, 'poll'):
             # an open-ended polling source (the queue worker): poll(block) -> request dict | None, StopIteration when closed
@@ -363,7 +378,8 @@ class HvxLLM:
                 max_out = max([r.max_len for r in it] + [1])
                 max_prefix = max([len(r.prefix) for r in it] + [1])
                 it = iter(it)
-        eng = _DecodeEngine(self, n_slots=n_slots, max_out=max_out, max_prefix=max_prefix, pace=pace, mixed_sampling=mixed_sampling, win_cap=win_cap)
+        eng = _DecodeEngine(self, n_slots=n_slots, max_out=max_out, max_prefix=max_prefix, pace=pace, mixed_sampling=mixed_sampling, win_cap=win_cap,
+                            **(dict(mixed_heads=True, head_cap=head_cap) if mixed_heads else {}))
         gen = eng.run(it)
         try:
             for kind, r in gen:
@@ -421,9 +437,18 @@ class _DecodeEngine:
 
     MIXED_WIN_CAP = 64             # default ring capacity of a mixed-sampling grid (the sampler's LDS snapshot holds 256 entries: anything up to that stays on its fast path)
 
-    def __init__(self, llm, n_slots, max_out, max_prefix, stream_first=False, sync_every=None, pace=None, mixed_sampling=False, win_cap=None):
+    def __init__(self, llm, n_slots, max_out, max_prefix, stream_first=False, sync_every=None, pace=None, mixed_sampling=False, win_cap=None,
+                 mixed_heads=False, head_cap=None):
         import time
         self.mixed = bool(mixed_sampling)
+        self.mixed_heads = bool(mixed_heads)
+        if not self.mixed_heads and head_cap is not None:
+            raise ValueError('head_cap belongs to a mixed-heads grid (mixed_heads=True)')
+        if self.mixed_heads:
+            # rows per sequence of the grid: the most heads a request may ask for (the forward refuses more than the model has, the step loop more than 8)
+            head_cap = int(llm.head_num if head_cap is None else head_cap)
+            if not 1 <= head_cap <= min(int(llm.head_num), 8):
+                raise ValueError('head_cap=%r outside [1, %d]' % (head_cap, min(int(llm.head_num), 8)))
         if not self.mixed and win_cap is not None:
             raise ValueError('win_cap belongs to a mixed-sampling grid (mixed_sampling=True)')
         if self.mixed and win_cap is not None and int(win_cap) < 1:
@@ -432,8 +457,8 @@ class _DecodeEngine:
         if self.pace is not None and (len(self.pace) != 3 or self.pace[0] < 1 or self.pace[1] < 1 or self.pace[2] < 0):
             raise ValueError('pace = (first >= 1, every_steps >= 1, more >= 0), got %r' % (pace,))       # (first == 0 would leave the idle grid spinning)
         self.llm, self.S, self.max_out = llm, int(n_slots), int(max_out)
-        self.max_prefix = max(int(max_prefix), self.S * llm.head_k())
-        self.K = llm.head_k()
+        self.K = head_cap if self.mixed_heads else llm.head_k()
+        self.max_prefix = max(int(max_prefix), self.S * self.K)
         self.sp = sampling_params(llm.sampling)
         self.thr = rep_threshold(self.sp['win_size'], self.sp['tau_r'])
         self.stream_first = stream_first
@@ -497,6 +522,15 @@ class _DecodeEngine:
                 self.seq = _lib.SeqSampling()
                 self.seq.top_k, self.seq.top_p = self.seq_top_k.data_ptr(), self.seq_top_p.data_ptr()
                 self.seq.win_size, self.seq.rep_thresh = self.seq_win.data_ptr(), self.seq_thr.data_ptr()
+            self.hd = None
+            if self.mixed_heads:
+                # the head count per slot, at a fixed address like the rest: hvx_llm_decode_join_mixed writes a slot's entry, the captured step reads it
+                self.seq_heads = torch.full((S,), min(llm.head_k(), K), dtype=torch.int32, device=dev)
+                self.hd = _lib.SeqHeads()
+                self.hd.head_k = self.seq_heads.data_ptr()
+        self.head_steps = {}                     # heads_live -> decode steps enqueued with it (a mixed-heads grid)
+        self.head_runs = []                      # the same in order: [heads_live, steps] per run of blocks with one value
+        self.heads_live = 1
         self.slot_req = [None] * S
         self.joins = []                          # (tag, slot) of every request that joined, in order
         self.join_block = [0] * S                # blocks launched when the slot's request joined: older snapshots describe its predecessor
@@ -554,10 +588,19 @@ class _DecodeEngine:
         """(parameters, repetition threshold) request r samples with: its own, or the engine's defaults"""
         return (self.sp, self.thr) if r.sp is None else (r.sp, r.thr)
 
+    def _heads_of(self, r):
+        """heads request r decodes with: its own inference_head_num, or the LM's, under the reference's rule"""
+        n = getattr(r, 'heads', None)
+        return effective_heads(self.llm.inference_head_num if n is None else n, self.llm.head_num)
+
     def _refuse(self, r):
         """None, or the error that keeps request r off the grid"""
         if getattr(r, 'sp_error', None) is not None:
             return r.sp_error
+        if getattr(r, 'heads', None) is not None and not self.mixed_heads:
+            return ValueError('the request carries its own inference_head_num but the decode grid was not started with mixed_heads=True')
+        if self.mixed_heads and self._heads_of(r) > self.K:
+            return ValueError("inference_head_num=%d exceeds the grid's head_cap=%d" % (self._heads_of(r), self.K))
         if getattr(r, 'sp', None) is not None and not self.mixed:
             return ValueError('the request carries its own sampling parameters but the decode grid was not started with mixed_sampling=True')
         if self.mixed:
@@ -602,7 +645,13 @@ class _DecodeEngine:
             ctrl = self._h2d([i, 0, n, n, n - 1], torch.int32)
             llm._forward(1, n, tok, ctrl, 0, None)
         r.pos = n
-        if self.mixed:
+        if self.mixed_heads:
+            sp, thr = self._sampling_of(r)
+            r.k = self._heads_of(r)
+            check(llm.lib.hvx_llm_decode_join_mixed(llm._h, C.c_void_p(self.stream.cuda_stream), C.byref(self.args), C.byref(self.seq) if self.mixed else None,
+                                                    C.byref(self.hd), i, int(r.prefix[-1]), n, r.min_len, r.max_len, sp['top_k'], sp['top_p'], sp['win_size'], thr,
+                                                    r.k), 'hvx_llm_decode_join_mixed')
+        elif self.mixed:
             sp, thr = self._sampling_of(r)
             check(llm.lib.hvx_llm_decode_join_seq(llm._h, C.c_void_p(self.stream.cuda_stream), C.byref(self.args), C.byref(self.seq), i, int(r.prefix[-1]), n,
                                                   r.min_len, r.max_len, sp['top_k'], sp['top_p'], sp['win_size'], thr), 'hvx_llm_decode_join_seq')
@@ -666,7 +715,20 @@ class _DecodeEngine:
             with torch.cuda.stream(stream):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
-                if self.mixed:
+                if self.mixed_heads:
+                    # heads the block computes: the widest request in flight (conservative: a finished sequence counts until the host has seen it
+                    # finish; an idle grid keeps the last value rather than capture a graph for nothing)
+                    live_k = [r.k for r in self.slot_req if r is not None and not r.done]
+                    if live_k:
+                        self.heads_live = max(live_k)
+                    self.head_steps[self.heads_live] = self.head_steps.get(self.heads_live, 0) + sync_every
+                    if self.head_runs and self.head_runs[-1][0] == self.heads_live:
+                        self.head_runs[-1][1] += sync_every
+                    else:
+                        self.head_runs.append([self.heads_live, sync_every])
+                    check(llm.lib.hvx_llm_decode_steps_mixed(llm._h, C.c_void_p(stream.cuda_stream), C.byref(self.args), C.byref(self.seq) if self.mixed else None,
+                                                             C.byref(self.hd), self.heads_live, sync_every), 'hvx_llm_decode_steps_mixed')
+                elif self.mixed:
                     check(llm.lib.hvx_llm_decode_steps_seq(llm._h, C.c_void_p(stream.cuda_stream), C.byref(self.args), C.byref(self.seq), sync_every),
                           'hvx_llm_decode_steps_seq')
                 else:
@@ -681,7 +743,7 @@ class _DecodeEngine:
                 slot['done'].record(stream)
 
         def steps_needed(r):
-            return max(0, -(-(min(r.min_len, r.max_len) - r.state[1]) // K))
+            return max(0, -(-(min(r.min_len, r.max_len) - r.state[1]) // (r.k if self.mixed_heads else K)))
 
         def grow_ring():
             """one step needs more values than the ring holds (toy capacities only): quadruple it, keeping the unread values"""
@@ -883,8 +945,11 @@ class _DecodeEngine:
                               requests=n_done, prefill_and_setup_seconds=t_setup,
                               device_idle_ms_between_blocks=sum(gaps), idle_gaps_over_1ms=[(i, round(g, 1)) for i, g in enumerate(gaps) if g > 1.0][:24], decode_step_us=1e3 * step_ms, decode_steps_timed=n_blk * sync_every,
                               mean_active_sequences=seqs, mean_ctx=ctx_sum / seqs if seqs else 0.0,
-                              decode_step_bytes=llm.decode_step_bytes(1, K, ctx_sum), clean=finished_clean, mixed_sampling=self.mixed)
-            if self.mixed:
+                              decode_step_bytes=llm.decode_step_bytes(1, K, ctx_sum), clean=finished_clean, mixed_sampling=self.mixed, mixed_heads=self.mixed_heads)
+            if self.mixed_heads:
+                # rows: the backbone's grid; the bf16 decode GEMM forms cover 33..256 rows, a wider grid runs the general forms
+                self.stats.update(head_cap=K, head_steps=dict(self.head_steps), head_runs=[tuple(x) for x in self.head_runs], rows=S * K)
+            if self.mixed or self.mixed_heads:
                 self.stats['joins'] = list(self.joins)        # (tag, slot) in join order: which request took over whose slot
 
 

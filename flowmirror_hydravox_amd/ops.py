@@ -236,10 +236,12 @@ def seq_sampling_block(seq_params, n_seq, device):
 
 
 def ras_sample(logp, hist, hist_len, min_len, noise, cursor, *, speech_tokens, top_k=25, top_p=0.8, win_size=10, rep_thresh=1, active=None,
-               max_trials=100, seq_params=None, seq_entry=None):
+               max_trials=100, seq_params=None, seq_entry=None, seq_heads=None, mixed_entry=None):
     """logp f32 [S][K][V]; hist int32 [S][Hcap]; hist_len/min_len int32 [S]; noise f32 [S][Ncap]; cursor int64 [S] (updated in place)
     -> ids int32 [S][K].  seq_params: dict of four [S] tensors (top_k, top_p, win_size, rep_thresh) — every sequence samples with its own
-    values and the scalar keywords are not read (hvx_ras_sample_seq).  seq_entry=True takes that entry point with a NULL block."""
+    values and the scalar keywords are not read (hvx_ras_sample_seq).  seq_entry=True takes that entry point with a NULL block.
+    seq_heads: [S] head counts — sequence s samples heads j < clamp(seq_heads[s], 1, K) only, the other ids come back -3
+    (hvx_ras_sample_mixed, with or without seq_params).  mixed_entry=True takes that entry point with a NULL heads block."""
     lib = _lib.load()
     S, K, V = logp.shape
     out = torch.empty(S, K, dtype=torch.int32, device=logp.device)
@@ -251,7 +253,19 @@ def ras_sample(logp, hist, hist_len, min_len, noise, cursor, *, speech_tokens, t
     a.top_k, a.top_p, a.win_size, a.rep_thresh = top_k, top_p, win_size, rep_thresh
     a.noise, a.noise_seq_stride, a.noise_len = ptr(noise), noise.shape[1], noise.shape[1]
     a.cursor, a.out_ids, a.max_trials = ptr(cursor), ptr(out), max_trials
-    if seq_params is not None:
+    if seq_heads is not None or mixed_entry:
+        q = keep = None
+        if seq_params is not None:
+            q, keep = seq_sampling_block(seq_params, S, logp.device)
+        hd = None
+        if seq_heads is not None:
+            heads = torch.as_tensor(seq_heads).detach().reshape(-1).to(torch.int32).contiguous().to(logp.device)
+            if heads.numel() != S:
+                raise ValueError('seq_heads has %d entries for %d sequences' % (heads.numel(), S))
+            hd = _lib.SeqHeads()
+            hd.head_k = heads.data_ptr()
+        check(lib.hvx_ras_sample_mixed(C.byref(a), None if q is None else C.byref(q), None if hd is None else C.byref(hd), stream_ptr()), 'hvx_ras_sample_mixed')
+    elif seq_params is not None:
         q, keep = seq_sampling_block(seq_params, S, logp.device)      # (`keep`: the arrays live until the launch is enqueued; the allocator reuses them in stream order)
         check(lib.hvx_ras_sample_seq(C.byref(a), C.byref(q), stream_ptr()), 'hvx_ras_sample_seq')
     elif seq_entry:

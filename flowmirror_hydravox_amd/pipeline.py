@@ -33,6 +33,7 @@ class Utterance:
     max_token_text_ratio: Optional[float] = None            # per-utterance overrides of the call's length ratios
     min_token_text_ratio: Optional[float] = None
     sampling: object = None                                 # own top_p / top_k / win_size / tau_r (dict or partial) in a mixed-sampling grid; None: the LM's
+    inference_head_num: Optional[int] = None                # own head count in a mixed-heads grid; None: the LM's
 
 
 @dataclass
@@ -286,7 +287,7 @@ class HvxPipeline:
 
     @torch.inference_mode()
     def serve(self, source, lm_slots=16, acoustic_batch=None, acoustic_min_batch=1, max_out=None, max_prefix=None,
-              max_token_text_ratio=20, min_token_text_ratio=2, pace=None, mixed_sampling=False, win_cap=None):
+              max_token_text_ratio=20, min_token_text_ratio=2, pace=None, mixed_sampling=False, win_cap=None, mixed_heads=False, head_cap=None):
         """The continuous engine over an open-ended SOURCE of utterances: `source.poll(block)` returns the next `Utterance`, or None when
         nothing is waiting (it is asked to block only while the decode grid is idle), and raises StopIteration when closed.  Generator over
         (utterance, waveform | exception, tokens) in completion order.
@@ -302,7 +303,8 @@ class HvxPipeline:
         sources implement it and re-serve the request); without `unpoll` it joins the abandoned list.
         `pace` = (first, every_steps, more): admission pacing of the decode grid (see _DecodeEngine.run).
         `mixed_sampling`: utterances may carry their own `sampling` and decode side by side with others' (HvxLLM.generate_stream; `win_cap` is
-        the longest repetition window the grid holds).  Off, an utterance that carries `sampling` comes back with an error."""
+        the longest repetition window the grid holds).  Off, an utterance that carries `sampling` comes back with an error.
+        `mixed_heads`: the same for `inference_head_num` (`head_cap`: rows per sequence of the grid, default the model's head_num)."""
         acoustic_batch = acoustic_batch or self.acoustic_batch
         acoustic_min_batch = max(1, min(int(acoustic_min_batch), acoustic_batch))
         import queue
@@ -361,6 +363,7 @@ class HvxPipeline:
                 n_seen[0] += 1
                 seen[tag] = u
                 return dict(text=u.text, prompt_text=u.prompt_text, prompt_speech_token=u.prompt_speech_token, seed=u.seed, tag=tag, sampling=u.sampling,
+                            inference_head_num=u.inference_head_num,
                             max_token_text_ratio=max_token_text_ratio if u.max_token_text_ratio is None else u.max_token_text_ratio,
                             min_token_text_ratio=min_token_text_ratio if u.min_token_text_ratio is None else u.min_token_text_ratio)
 
@@ -379,7 +382,8 @@ class HvxPipeline:
                 with torch.inference_mode():
                     t0 = time.time()
                     gen = self.llm.generate_stream(_Requests(), n_slots=lm_slots, max_out=max_out, max_prefix=max_prefix, pace=pace,
-                                                   **(dict(mixed_sampling=True, win_cap=win_cap) if mixed_sampling else {}))
+                                                   **(dict(mixed_sampling=True, win_cap=win_cap) if mixed_sampling else {}),
+                                                   **(dict(mixed_heads=True, head_cap=head_cap) if mixed_heads else {}))
                     try:
                         for tag, toks in gen:
                             if not put((tag, toks)):

@@ -96,15 +96,23 @@ class _TaskSource:
     mixed_sampling: top_p / top_k / win_size / tau_r are per-sequence state of the decode grid (HvxLLM.generate_stream(mixed_sampling=True)), so
     a task with other values joins the running epoch and its utterance carries them (`Utterance.sampling`; a task without extra_params
     carries None and takes the epoch's).  What still closes the epoch: another inference_head_num (it sets the grid's row count), a window
-    that a ring of `win_cap` entries cannot hold (0 = whole history, or more than win_cap), a top_k outside [1, 64], and everything above."""
+    that a ring of `win_cap` entries cannot hold (0 = whole history, or more than win_cap), a top_k outside [1, 64], and everything above.
+    mixed_heads: inference_head_num is per-sequence state too (HvxLLM.generate_stream(mixed_heads=True)): a task whose effective head count
+    (min(n, head_num), <= 0 -> 1) is in [1, head_cap] joins the running epoch and its utterance carries the task's value
+    (`Utterance.inference_head_num`); one above head_cap is carried to the next epoch.  Without mixed_sampling the four sampling values must
+    still be the epoch's."""
 
-    def __init__(self, mm, task_queue, result_dict, first, normalise, worker_id, mixed_sampling=False, win_cap=64):
+    def __init__(self, mm, task_queue, result_dict, first, normalise, worker_id, mixed_sampling=False, win_cap=64, mixed_heads=False, head_cap=None):
         self.mm, self.q, self.results, self.normalise, self.worker_id = mm, task_queue, result_dict, normalise, worker_id
         self.mixed, self.win_cap = bool(mixed_sampling), int(win_cap)
+        self.mixed_heads = bool(mixed_heads)
         self.key = _sampling_key(first)
         # the head count the epoch's grid is built with: the first task's, or (a first task without extra_params) what the model holds
         llm = (getattr(mm, 'models', None) or {}).get('llm')
         self.head_num = self.key[4] if first.get('extra_params') else getattr(llm, 'inference_head_num', None)
+        # a mixed-heads grid: the model's head count bounds a request's (None: unknown here, the engine applies it) and head_cap is the grid's rows per sequence
+        self.model_heads = getattr(llm, 'head_num', None)
+        self.head_cap = int(head_cap) if head_cap is not None else self.model_heads
         self.head = first
         self.carry = None
         self.stop = False
@@ -112,9 +120,21 @@ class _TaskSource:
 
     POLL_SECONDS = 0.1
 
+    def _heads_fit(self, ep):
+        """is the head count of these extra_params one a grid of head_cap rows per sequence holds?"""
+        from .llm import effective_heads
+        try:
+            n = int(ep['inference_head_num'])
+        except (KeyError, TypeError, ValueError):
+            return False
+        k = effective_heads(n, n if self.model_heads is None else self.model_heads)
+        return self.head_cap is None or k <= self.head_cap
+
     def _joins(self, t):
         """does task t (tts / zero_shot, not segmented) belong to this epoch?"""
         if not self.mixed:
+            if self.mixed_heads and t.get('extra_params') and _sampling_key(t)[:4] == self.key[:4]:
+                return self._heads_fit(t['extra_params'])
             return _sampling_key(t) == self.key
         ep = t.get('extra_params')
         if not ep:
@@ -123,6 +143,8 @@ class _TaskSource:
             fits = 1 <= int(ep['win_size']) <= self.win_cap and 1 <= int(ep['top_k']) <= 64
         except (KeyError, TypeError, ValueError):
             return False                               # (an incomplete set: served on its own, where the one-by-one rules answer it)
+        if self.mixed_heads:
+            return fits and self._heads_fit(ep)
         return fits and ep.get('inference_head_num') is not None and ep.get('inference_head_num') == self.head_num
 
     def unpoll(self, u):
@@ -158,6 +180,8 @@ class _TaskSource:
         if self.mixed and t.get('extra_params'):
             ep = t['extra_params']
             u.sampling = dict(top_p=ep['top_p'], top_k=ep['top_k'], win_size=ep['win_size'], tau_r=ep['tau_r'])
+        if self.mixed_heads and t.get('extra_params'):
+            u.inference_head_num = int(t['extra_params']['inference_head_num'])
         u.tag = t
         return u
 
@@ -189,7 +213,7 @@ class _TaskSource:
 
 
 def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_id, frontend_factory=None, lm_slots=None, acoustic_batch=4,
-                               mixed_sampling=False):
+                               mixed_sampling=False, mixed_heads=False):
     """Same wire format as worker_process_tts, served by the continuous-batching engine (replaces the one-request-at-a-time
     loop of server/worker.py:54-102 and what server/router.py:144-156 feeds it): `tts` / `zero_shot` tasks join ONE decode grid as they arrive
     (HvxPipeline.serve -> HvxLLM.generate_stream: the LM weights are streamed once per step for every request in flight, a finished request's
@@ -197,7 +221,8 @@ def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_
     others, and every result is written to `result_dict` the moment its waveform is complete.  `load_pt` and a change of sampling parameters
     are epoch boundaries (FIFO: see _TaskSource).  What bench.py measures is this path.
     mixed_sampling=True: requests with different top_p / top_k / win_size / tau_r share the grid, each sampling with its own values; only
-    another inference_head_num, a window over 64 (or 0) and the non-synthesis tasks remain epoch boundaries."""
+    another inference_head_num, a window over 64 (or 0) and the non-synthesis tasks remain epoch boundaries.
+    mixed_heads=True: requests with different inference_head_num share the grid as well (rows per sequence: the model's head_num)."""
     os.environ['CUDA_VISIBLE_DEVICES'] = str(worker_id % num_workers_gpu)
     from .model_manager import HvxModelManager
     from .pipeline import HvxPipeline
@@ -206,14 +231,17 @@ def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_
     mm = HvxModelManager(frontend_factory=frontend_factory)
     mm.load_models(argparse.Namespace(config=os.getenv('TTS_CONFIG'), model_dir=os.getenv('TTS_MODEL_DIR'), bf16=_env_flag('TTS_BF_16'),
                                       fp16=_env_flag('TTS_FP_16'), cpu=_env_flag('TTS_CPU', False)))
-    serve_queue(mm, task_queue, result_dict, worker_id, lm_slots=lm_slots, acoustic_batch=acoustic_batch, mixed_sampling=mixed_sampling)
+    serve_queue(mm, task_queue, result_dict, worker_id, lm_slots=lm_slots, acoustic_batch=acoustic_batch, mixed_sampling=mixed_sampling,
+                mixed_heads=mixed_heads)
 
 
-def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acoustic_batch=4, normalise=None, mixed_sampling=False, win_cap=64, token_log=None):
+def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acoustic_batch=4, normalise=None, mixed_sampling=False, win_cap=64, token_log=None,
+                mixed_heads=False, head_cap=None):
     """the loop of worker_process_tts_batched over an already loaded model manager (tests drive this directly).  Returns its counters:
     `epochs` (decode grids started) and `epoch_boundaries` (tasks that closed a running grid because they could not join it; the shutdown
-    sentinel is not one).  token_log: a dict that receives task id -> speech-token ids of every synthesised request."""
-    stats = dict(epochs=0, epoch_boundaries=0, mixed_sampling=bool(mixed_sampling))
+    sentinel is not one).  token_log: a dict that receives task id -> speech-token ids of every synthesised request.
+    mixed_heads / head_cap: see _TaskSource; llm.inference_head_num is still written at epoch start only (the first task's)."""
+    stats = dict(epochs=0, epoch_boundaries=0, mixed_sampling=bool(mixed_sampling), mixed_heads=bool(mixed_heads))
     from .pipeline import HvxPipeline
     from .sampling import ras_sampling
     normalise = normalise or _text_normaliser()
@@ -239,9 +267,10 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
                 result = {'error': str(e)}
             result_dict[task['id']] = result
             continue
-        src = _TaskSource(mm, task_queue, result_dict, task, normalise, worker_id, mixed_sampling=mixed_sampling, win_cap=win_cap)
-        if mixed_sampling and not src._joins(task):
-            # a request no mixed grid can hold (window 0 or over win_cap): an epoch of its own on the scalar engine, as without the switch
+        src = _TaskSource(mm, task_queue, result_dict, task, normalise, worker_id, mixed_sampling=mixed_sampling, win_cap=win_cap,
+                          **(dict(mixed_heads=True, head_cap=head_cap) if mixed_heads else {}))
+        if (mixed_sampling or mixed_heads) and not src._joins(task):
+            # a request no mixed grid can hold (window 0 or over win_cap, more heads than head_cap): an epoch of its own on the scalar engine, as without the switch
             src = _TaskSource(mm, task_queue, result_dict, task, normalise, worker_id)
         in_flight = {}
         stats['epochs'] += 1
@@ -249,6 +278,8 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
             apply_extra_params(mm, task, ras_sampling)
             pipe.llm = mm.models['llm']
             kw = dict(mixed_sampling=True, win_cap=win_cap) if src.mixed else {}
+            if src.mixed_heads:
+                kw.update(mixed_heads=True, head_cap=head_cap)
             for u, wav, toks in pipe.serve(_Tracked(src, in_flight), lm_slots=lm_slots, acoustic_batch=acoustic_batch, acoustic_min_batch=1, **kw):
                 t = u.tag
                 in_flight.pop(t['id'], None)

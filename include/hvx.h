@@ -91,6 +91,15 @@ typedef struct {
 } hvx_seq_sampling;
 /* hvx_ras_sample with a sampling block; q == NULL is hvx_ras_sample */
 int hvx_ras_sample_seq(const hvx_sample_args* a, const hvx_seq_sampling* q, hvx_stream s);
+/* Per-sequence head counts: one device array of [n_seq] entries.  The reference sets inference_head_num per REQUEST too
+ * (server/worker.py:57-65); with this block sequence i samples and accepts heads j < clamp(head_k[i], 1, a->head_k) only.  The other heads of
+ * the sequence consume no noise, their log-prob rows are never read, and their out_ids entries are -3 ("no head"); a sequence that ran out
+ * of noise still gets -2 in all a->head_k entries.  The row strides (out_ids, tok, log-probs) stay a->head_k. */
+typedef struct {
+    const int32_t* head_k;
+} hvx_seq_heads;
+/* hvx_ras_sample_seq with a heads block; heads == NULL is hvx_ras_sample_seq (q may be NULL as there) */
+int hvx_ras_sample_mixed(const hvx_sample_args* a, const hvx_seq_sampling* q, const hvx_seq_heads* heads, hvx_stream s);
 
 /* ---------------------------------------------------------------------------------------------------
  * Building-block operators (exported for the parity tests; the model entry points below are chains of these)
@@ -302,6 +311,13 @@ int hvx_llm_decode_steps(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, int
  * sequence's repetition ring is win_size[i] entries long (clamped to [1, win_cap]): slot = out_len % win_size[i], hist_len =
  * min(out_len, win_size[i]) — the ring holds exactly the last min(win_size[i], out_len) tokens the sampler counts over, wrapped or not. */
 int hvx_llm_decode_steps_seq(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, const hvx_seq_sampling* q, int32_t n_steps);
+/* The same loop with per-sequence head counts as well (heads == NULL and heads_live == a->head_k is hvx_llm_decode_steps_seq; q may be NULL).
+ * a->head_k is the grid's head CAPACITY: rows per sequence and the [n_seq][head_k][vocab] log-prob layout.  heads_live in [1, a->head_k] is how
+ * many MTP heads the forward computes — the heads' GEMMs are launched for heads_live heads, the weights of the others are not streamed — and
+ * must be at least the largest head_k[i] of a live sequence (the caller's duty: the count of a finished sequence does not matter).  The
+ * cached step graph is keyed on the heads array and on heads_live, one graph per value. */
+int hvx_llm_decode_steps_mixed(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, const hvx_seq_sampling* q, const hvx_seq_heads* heads,
+                               int32_t heads_live, int32_t n_steps);
 /* Continuous batching — the batching scheduler SURVEY.md §8(f) N1 asks for in place of the reference's one-request-at-a-time worker loop
  * (server/worker.py:54-102): between two hvx_llm_decode_steps calls on the same stream a new sequence takes over slot `slot` of the grid
  * described by `a` (a finished sequence's slot, or one that was never used).  The caller has prefilled all but the last prefix row into
@@ -316,6 +332,12 @@ int hvx_llm_decode_join(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, int3
  * rep_thresh < 0. */
 int hvx_llm_decode_join_seq(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, const hvx_seq_sampling* q, int32_t slot, int32_t first_tok,
                             int32_t pos, int32_t min_len, int32_t max_len, int32_t top_k, float top_p, int32_t win_size, int32_t rep_thresh);
+/* The join of a grid with per-sequence head counts: head_k is written to heads->head_k[slot] by the same kernel.  The four sampling values
+ * are read only when q is given (q == NULL: the scalar sampling of `a`), head_k only when heads is given.  Refused — -1, hvx_last_error,
+ * nothing launched — when head_k is outside [1, a->head_k], and for the sampling values as hvx_llm_decode_join_seq. */
+int hvx_llm_decode_join_mixed(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, const hvx_seq_sampling* q, const hvx_seq_heads* heads,
+                              int32_t slot, int32_t first_tok, int32_t pos, int32_t min_len, int32_t max_len, int32_t top_k, float top_p,
+                              int32_t win_size, int32_t rep_thresh, int32_t head_k);
 /* debugging / parity: copy the post-final-norm hidden of the last rows of the previous forward (fp32 [n_seq][H]) */
 int hvx_llm_last_hidden(hvx_llm* h, hvx_stream s, int32_t n_seq, float* out);
 

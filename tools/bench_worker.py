@@ -3,11 +3,14 @@
 bench workload: N `tts` tasks of 512 text tokens pushed through a queue, HydraVox-CV3 bf16 LM + flow, fp32-contract vocoder, seeded random
 weights; a stand-in frontend turns the task text into token ids (the real text / audio frontends are outside this build).
 
-    python tools/bench_worker.py [--tasks 64] [--chars 512] [--lm-slots 64] [--acoustic-batch 4] [--one-by-one] [--alternate-sampling] [--mixed-sampling]
+    python tools/bench_worker.py [--tasks 64] [--chars 512] [--lm-slots 64] [--acoustic-batch 4] [--one-by-one] [--alternate-sampling] [--mixed-sampling] [--alternate-heads] [--mixed-heads]
 
 --alternate-sampling: the tasks carry `extra_params` that alternate between two sampling parameter sets (same inference_head_num) — the worst
 case for the worker's epochs: without --mixed-sampling every task closes the running decode grid.  --mixed-sampling serves the queue with
 serve_queue(mixed_sampling=True): the parameters are per-sequence state of the grid and the tasks share it.
+--alternate-heads: the tasks carry `extra_params` that alternate between two head counts (2 and 5, same sampling parameters); without
+--mixed-heads every task closes the running grid, with it (serve_queue(mixed_heads=True)) they share one grid of head_num rows per sequence.
+The A/B is four runs — off, on, off, on — each in its own process on the same box.
 """
 import argparse
 import json
@@ -30,6 +33,8 @@ ap.add_argument('--acoustic-batch', type=int, default=4)
 ap.add_argument('--one-by-one', action='store_true', help='the reference loop instead: worker_process_tts semantics, one task at a time')
 ap.add_argument('--alternate-sampling', action='store_true', help='tasks alternate between two sampling parameter sets (extra_params)')
 ap.add_argument('--mixed-sampling', action='store_true', help='serve_queue(mixed_sampling=True): requests with different sampling parameters share the grid')
+ap.add_argument('--alternate-heads', action='store_true', help='tasks alternate between two head counts (extra_params.inference_head_num = 2 / 5)')
+ap.add_argument('--mixed-heads', action='store_true', help='serve_queue(mixed_heads=True): requests with different head counts share the grid')
 a = ap.parse_args()
 from flowmirror_hydravox_amd import cv3_config, weights as W  # noqa: E402
 from flowmirror_hydravox_amd.flow import HvxFlow  # noqa: E402
@@ -77,6 +82,8 @@ def run(n, one_by_one):
         t = dict(id=i, task_type='tts', text=str(i), speaker_id='s', seed=i)
         if a.alternate_sampling:
             t['extra_params'] = dict(SETS[i % 2])
+        if a.alternate_heads:
+            t['extra_params'] = dict(t.get('extra_params') or SETS[1], inference_head_num=(2, 5)[i % 2])
         q.put(t)
     q.put(None)
     torch.cuda.synchronize()
@@ -91,11 +98,13 @@ def run(n, one_by_one):
             if 'extra_params' in t:
                 ep = t['extra_params']
                 llm.sampling = partial(ras_sampling, top_p=ep['top_p'], top_k=ep['top_k'], win_size=ep['win_size'], tau_r=ep['tau_r'])
+                llm.inference_head_num = ep['inference_head_num']
             out = _synthesize(mm, mm.frontend.frontend_sft(t['text'], t['speaker_id']), 1.0, zero_shot=False)
             results[t['id']] = {'output_audio': out, 'duration': out.shape[-1] / 24000}
         llm.inference = orig
     else:
-        counters.update(serve_queue(mm, q, results, lm_slots=a.lm_slots, acoustic_batch=a.acoustic_batch, normalise=lambda s: s, mixed_sampling=a.mixed_sampling) or {})
+        counters.update(serve_queue(mm, q, results, lm_slots=a.lm_slots, acoustic_batch=a.acoustic_batch, normalise=lambda s: s, mixed_sampling=a.mixed_sampling,
+                                    mixed_heads=a.mixed_heads) or {})
     torch.cuda.synchronize()
     dt = time.time() - t0
     assert len(results) == n and all('output_audio' in r for r in results.values()), [r for r in results.values() if 'error' in r][:2]
@@ -108,4 +117,4 @@ dt, audio = run(a.tasks, a.one_by_one)
 print(json.dumps({'path': 'worker_process_tts (one task at a time, reference loop)' if a.one_by_one else 'worker.serve_queue (continuous engine)', 'tasks': a.tasks,
                   'chars': a.chars, 'seconds': round(dt, 2), 'requests_per_s': round(a.tasks / dt, 3), 'speech_tokens_per_s': round(a.tasks * n_spk / dt, 1),
                   'rtf': round(dt / audio, 6), 'lm_slots': a.lm_slots, 'acoustic_batch': a.acoustic_batch, 'alternate_sampling': a.alternate_sampling,
-                  'mixed_sampling': a.mixed_sampling, 'epochs': counters.get('epochs'), 'epoch_boundaries': counters.get('epoch_boundaries')}))
+                  'mixed_sampling': a.mixed_sampling, 'alternate_heads': a.alternate_heads, 'mixed_heads': a.mixed_heads, 'epochs': counters.get('epochs'), 'epoch_boundaries': counters.get('epoch_boundaries')}))
