@@ -213,6 +213,10 @@ SYMBOLS = {
     'hvx_flow_set_f16_linears': (c_i32, [c_vp, c_i32]),
     'hvx_flow_set_f32_small': (c_i32, [c_vp, c_i32]),
     'hvx_cfm_solve_batch': (c_i32, [c_vp, c_vp, c_vp, c_sz, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, C.POINTER(c_f32), C.POINTER(c_f32), c_i32]),
+    # (t_len, covered, cache_ld, cache_fill: HOST int32 arrays; cache: a HOST array of device pointers)
+    'hvx_cfm_solve_stream_batch': (c_i32, [c_vp, c_vp, c_vp, c_sz, c_i32, c_i32, C.POINTER(c_i32), c_vp, c_vp, c_vp, c_vp, c_i32, C.POINTER(c_f32),
+                                           C.POINTER(c_f32), c_i32, C.POINTER(c_i32), C.POINTER(c_vp), C.POINTER(c_i32), C.POINTER(c_i32)]),
+    'hvx_op_mel_cache_append': (c_i32, [c_vp, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_vp), C.POINTER(c_i32), C.POINTER(c_i32), c_vp]),
     'hvx_cfm_solve': (c_i32, [c_vp, c_vp, c_vp, c_sz, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, C.POINTER(c_f32), C.POINTER(c_f32)]),
     'hvx_matcha_create': (c_i32, [C.POINTER(MatchaConfig), C.POINTER(c_vp), c_i32, C.POINTER(c_vp)]),
     'hvx_matcha_destroy': (None, [c_vp]),
@@ -254,7 +258,8 @@ SYMBOLS = {
 # 7 — no struct changed and no existing symbol changed meaning, and a library of version 7 built before it fails in load() below on the missing symbol, with the
 # rebuild command, exactly as a version mismatch would.  The per-sequence sampling entry points (hvx_ras_sample_seq, hvx_llm_decode_steps_seq,
 # hvx_llm_decode_join_seq and their hvx_seq_sampling block) joined the same way: additive, no existing struct or symbol touched; so did the
-# per-sequence head counts (hvx_ras_sample_mixed, hvx_llm_decode_steps_mixed, hvx_llm_decode_join_mixed and hvx_seq_heads).
+# per-sequence head counts (hvx_ras_sample_mixed, hvx_llm_decode_steps_mixed, hvx_llm_decode_join_mixed and hvx_seq_heads), and the streaming batch of the
+# serving engine (hvx_cfm_solve_stream_batch, hvx_op_mel_cache_append).
 HVX_ABI_VERSION = 7
 
 _lib = None

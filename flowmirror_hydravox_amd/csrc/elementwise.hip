@@ -597,6 +597,55 @@ int launch_resample_linear(const float* x, int rows, int t_in, float* y, int t_o
     return hipGetLastError() == hipSuccess ? 0 : (set_error("resample_linear launch failed"), -1);
 }
 
+// cache[i][ch][fill_i + (t - covered_i)] = x[first + i][ch][t] for covered_i <= t < t_len_i: grid (ceil(t_max / 256), mel, sessions of this launch).  The column
+// offset fill_i - covered_i is arbitrary, so the stores are single dwords (no alignment of a cache row is assumed); frames at or beyond t_len_i are never read.
+__global__ void mel_cache_append_kernel(MelAppendArgs a) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y, i = blockIdx.z;
+    const int cov = a.covered[i], tl = a.t_len[i];
+    if (t < cov || t >= tl) return;
+    a.cache[i][(long long)ch * a.ld[i] + a.fill[i] + (t - cov)] = a.x[((long long)i * a.mel + ch) * a.t_max + t];
+}
+int check_mel_cache_append(const char* who, int n, int mel, int t_max, const int* t_len, const int* covered, float* const* cache, const int* cache_ld,
+                           const int* cache_fill) {
+    if (n < 1) return set_error("%s: %d sessions", who, n), -1;
+    if (mel <= 0 || t_max <= 0 || mel > 65535) return set_error("%s: mel=%d, t_max=%d", who, mel, t_max), -1;
+    if (!covered || !cache || !cache_ld || !cache_fill) return set_error("%s: null argument", who), -1;
+    for (int i = 0; i < n; ++i) {
+        const int tl = t_len ? t_len[i] : t_max;
+        if (!cache[i]) return set_error("%s: session %d has no cache plane", who, i), -1;
+        if (tl < 0 || tl > t_max) return set_error("%s: session %d: t_len=%d outside [0, t_max=%d]", who, i, tl, t_max), -1;
+        if (covered[i] < 0 || covered[i] > tl) return set_error("%s: session %d: covered=%d outside [0, t_len=%d]", who, i, covered[i], tl), -1;
+        if (cache_fill[i] < 0 || cache_ld[i] <= 0 || (long long)cache_fill[i] + tl - covered[i] > cache_ld[i])
+            return set_error("%s: session %d: %d frames at column %d overflow a cache row of %d", who, i, tl - covered[i], cache_fill[i], cache_ld[i]), -1;
+    }
+    return 0;
+}
+int launch_mel_cache_append(const float* x, int n, int mel, int t_max, const int* t_len, const int* covered, float* const* cache, const int* cache_ld,
+                            const int* cache_fill, hipStream_t s) {
+    if (!x) return set_error("mel_cache_append: null input"), -1;
+    if (check_mel_cache_append("mel_cache_append", n, mel, t_max, t_len, covered, cache, cache_ld, cache_fill)) return -1;
+    for (int first = 0; first < n; first += MEL_APPEND_MAX) {
+        const int cnt = n - first < MEL_APPEND_MAX ? n - first : MEL_APPEND_MAX;
+        MelAppendArgs a = {};
+        a.x = x + (long long)first * mel * t_max;
+        a.mel = mel;
+        a.t_max = t_max;
+        int widest = 0;                            // frames of the longest session of this launch: the grid stops there
+        for (int i = 0; i < cnt; ++i) {
+            a.cache[i] = cache[first + i];
+            a.t_len[i] = t_len ? t_len[first + i] : t_max;
+            a.covered[i] = covered[first + i];
+            a.ld[i] = cache_ld[first + i];
+            a.fill[i] = cache_fill[first + i];
+            if (a.t_len[i] > a.covered[i] && a.t_len[i] > widest) widest = a.t_len[i];
+        }
+        if (widest == 0) continue;                 // nothing to append in this group
+        hipLaunchKernelGGL(mel_cache_append_kernel, dim3((widest + 255) / 256, mel, cnt), dim3(256), 0, s, a);
+        if (hipGetLastError() != hipSuccess) return set_error("mel_cache_append launch failed"), -1;
+    }
+    return 0;
+}
+
 template <class D>
 __global__ void rows_to_dtype_kernel(const float* src, int ld_src, D* dst, int ld_dst, int cols, int cols_pad) {
     const int r = blockIdx.x;

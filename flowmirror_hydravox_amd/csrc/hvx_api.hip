@@ -310,6 +310,11 @@ int hvx_op_resample_sinc(const float* x, int32_t rows, int32_t len, int64_t x_ro
     return launch_resample_sinc(x, rows, len, x_row_stride, taps, orig, new_, width, y, out_len, y_row_stride, (hipStream_t)s);      // (refuses what it cannot tile)
 }
 
+int hvx_op_mel_cache_append(const float* x, int32_t n, int32_t mel, int32_t t_max, const int32_t* t_len, const int32_t* covered, float* const* cache,
+                            const int32_t* cache_ld, const int32_t* cache_fill, hvx_stream s) {
+    return launch_mel_cache_append(x, n, mel, t_max, t_len, covered, cache, cache_ld, cache_fill, (hipStream_t)s);      // (refuses before it launches)
+}
+
 int hvx_op_skinny_gemm(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* Wpacked, const float* bias,
                        int32_t split_k, float* part_ws, float* out_f32, int32_t ldo, hvx_stream s) {
     if (dtype != DT_F32 && dtype != DT_BF16) return set_error("hvx_op_skinny_gemm: dtype %d: fp32 (0) or bf16 (1) only", dtype), -1;

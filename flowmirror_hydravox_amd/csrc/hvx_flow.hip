@@ -466,9 +466,17 @@ __global__ void kv_len_pair_kernel(const int* t_len, int* kv, int n, int T) {
     if (i < 2 * n) kv[i] = t_len ? t_len[i % n] : T;
 }
 
-int hvx_cfm_solve_batch(hvx_flow* h, hvx_stream stream, void* ws, size_t ws_bytes, int32_t n, int32_t T, const int32_t* t_len, float* x,
-                        const float* mu, const float* spks, const float* cond, int32_t n_steps, const float* t_steps, const float* dt_steps,
-                        int32_t static_chunk_size) {
+// the same from HOST values (a streaming batch knows its lengths on the host): up to MEL_APPEND_MAX of them per launch, by value
+struct KvVals { int v[MEL_APPEND_MAX]; };
+__global__ void kv_len_pair_vals_kernel(KvVals a, int* kv, int n, int first, int cnt) {
+    const int i = threadIdx.x;
+    if (i < cnt) kv[first + i] = kv[n + first + i] = a.v[i];
+}
+
+// t_len: device lengths (hvx_cfm_solve_batch) or t_len_host: the same on the host (hvx_cfm_solve_stream_batch); neither: every utterance has T frames
+static int solve_batch_impl(hvx_flow* h, hvx_stream stream, void* ws, size_t ws_bytes, int32_t n, int32_t T, const int32_t* t_len, const int32_t* t_len_host,
+                            float* x, const float* mu, const float* spks, const float* cond, int32_t n_steps, const float* t_steps, const float* dt_steps,
+                            int32_t static_chunk_size) {
     hipStream_t s = (hipStream_t)stream;
     if (!h) return set_error("hvx_cfm_solve: null handle"), -1;
     const hvx_flow_config& c = h->c;
@@ -492,6 +500,14 @@ int hvx_cfm_solve_batch(hvx_flow* h, hvx_stream stream, void* ws, size_t ws_byte
     const int* kv = nullptr;
     if (t_len) {
         hipLaunchKernelGGL(kv_len_pair_kernel, dim3((B + 63) / 64), dim3(64), 0, s, t_len, b.kv_in, n, T);
+        kv = b.kv_in;
+    } else if (t_len_host) {
+        for (int first = 0; first < n; first += MEL_APPEND_MAX) {
+            KvVals v;
+            const int cnt = n - first < MEL_APPEND_MAX ? n - first : MEL_APPEND_MAX;
+            for (int i = 0; i < MEL_APPEND_MAX; ++i) v.v[i] = i < cnt ? t_len_host[first + i] : 0;
+            hipLaunchKernelGGL(kv_len_pair_vals_kernel, dim3(1), dim3(64), 0, s, v, b.kv_in, n, first, cnt);
+        }
         kv = b.kv_in;
     }
     for (int st = 0; st < n_steps; ++st) {
@@ -530,6 +546,25 @@ int hvx_cfm_solve_batch(hvx_flow* h, hvx_stream stream, void* ws, size_t ws_byte
         HIP_OK(hipGetLastError());
     }
     return 0;
+}
+
+int hvx_cfm_solve_batch(hvx_flow* h, hvx_stream stream, void* ws, size_t ws_bytes, int32_t n, int32_t T, const int32_t* t_len, float* x,
+                        const float* mu, const float* spks, const float* cond, int32_t n_steps, const float* t_steps, const float* dt_steps,
+                        int32_t static_chunk_size) {
+    return solve_batch_impl(h, stream, ws, ws_bytes, n, T, t_len, nullptr, x, mu, spks, cond, n_steps, t_steps, dt_steps, static_chunk_size);
+}
+
+int hvx_cfm_solve_stream_batch(hvx_flow* h, hvx_stream stream, void* ws, size_t ws_bytes, int32_t n, int32_t T, const int32_t* t_len, float* x,
+                               const float* mu, const float* spks, const float* cond, int32_t n_steps, const float* t_steps, const float* dt_steps,
+                               int32_t static_chunk_size, const int32_t* covered, float* const* cache, const int32_t* cache_ld, const int32_t* cache_fill) {
+    if (!h) return set_error("hvx_cfm_solve_stream_batch: null handle"), -1;
+    // the caches' geometry is refused here, before the solve launches anything
+    if (check_mel_cache_append("hvx_cfm_solve_stream_batch", n, h->c.mel, T, t_len, covered, cache, cache_ld, cache_fill)) return -1;
+    if (t_len)
+        for (int i = 0; i < n; ++i)
+            if (t_len[i] < 1) return set_error("hvx_cfm_solve_stream_batch: session %d has no frames", i), -1;
+    if (solve_batch_impl(h, stream, ws, ws_bytes, n, T, nullptr, t_len, x, mu, spks, cond, n_steps, t_steps, dt_steps, static_chunk_size)) return -1;
+    return launch_mel_cache_append(x, n, h->c.mel, T, t_len, covered, cache, cache_ld, cache_fill, (hipStream_t)stream);
 }
 
 int hvx_cfm_solve_streaming(hvx_flow* h, hvx_stream stream, void* ws, size_t ws_bytes, int32_t T, float* x, const float* mu, const float* spks,

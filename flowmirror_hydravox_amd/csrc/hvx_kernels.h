@@ -238,6 +238,19 @@ int launch_resample_sinc(const float* x, int rows, int len, long long x_rs, cons
                          hipStream_t s);
 int launch_transpose_f32(const float* src, float* dst, int rows, int cols, int ld_src, int ld_dst, hipStream_t s);   // dst[c][r] = src[r][c]
 int launch_rows_to_dtype(const float* src, int ld_src, void* dst, int dst_dtype, int ld_dst, int rows, int cols, int cols_pad, hipStream_t s);
+// Streaming mel caches (hvx_cfm_solve_stream_batch): frames [covered[i], t_len[i]) of the `mel` rows of x[i] ((n, mel, t_max) f32) go to columns
+// [cache_fill[i], ...) of session i's cache plane cache[i] ((mel, cache_ld[i]) f32).  All per-session arrays are HOST arrays: the values travel by value in an
+// argument block of MEL_APPEND_MAX sessions, more sessions are further launches.  check_...: 0, or -1 with the error set; nothing is launched by it.
+#define MEL_APPEND_MAX 16
+struct MelAppendArgs {
+    const float* x; int mel, t_max;
+    float* cache[MEL_APPEND_MAX];
+    int t_len[MEL_APPEND_MAX], covered[MEL_APPEND_MAX], ld[MEL_APPEND_MAX], fill[MEL_APPEND_MAX];
+};
+int check_mel_cache_append(const char* who, int n, int mel, int t_max, const int* t_len, const int* covered, float* const* cache, const int* cache_ld,
+                           const int* cache_fill);
+int launch_mel_cache_append(const float* x, int n, int mel, int t_max, const int* t_len, const int* covered, float* const* cache, const int* cache_ld,
+                            const int* cache_fill, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // Sampler (common.py:138-166 + llm_multi_head_v3.py:151-166, 890-900)

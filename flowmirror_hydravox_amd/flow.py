@@ -314,6 +314,45 @@ class HvxFlow:
                                            self.static_chunk_size if streaming else 0), 'hvx_cfm_solve_batch')
         return [x[i, :, :lens[i]] for i in range(n_utt)]
 
+    def solve_stream_batch(self, mus, spks, conds, covered, caches, cache_fill, streaming=True, n_timesteps=None):
+        """Chunk jobs of several streaming sessions in ONE padded solve (hvx_cfm_solve_stream_batch): session i's prefix mu / cond (mel, T_i) and spk (mel,) are
+        solved as solve_batch solves them (chunk mask when `streaming`), then frames [covered[i], T_i) go into its cache plane caches[i] ((mel, ld_i) fp32,
+        contiguous) from column cache_fill[i] on.  `streaming` may be a list (a session's final job runs with the full mask, as `stream_tts`' last call): a
+        mixed call is split here into two solves, the attention kernels know one mask mode per launch.  Returns the number of frames appended per session."""
+        n_utt = len(mus)
+        flags = list(streaming) if isinstance(streaming, (list, tuple)) else [bool(streaming)] * n_utt
+        if len(set(flags)) > 1:
+            fresh = [0] * n_utt
+            for mode in (True, False):
+                idx = [i for i in range(n_utt) if bool(flags[i]) == mode]
+                pick = lambda v: [v[i] for i in idx]
+                for i, f in zip(idx, self.solve_stream_batch(pick(mus), pick(spks), pick(conds), pick(covered), pick(caches), pick(cache_fill), mode, n_timesteps)):
+                    fresh[i] = f
+            return fresh
+        from .ops import mel_append_block
+        lens = [int(m.shape[-1]) for m in mus]
+        T = max(lens) if lens else 0
+        mel, dev = self.cfg.mel, self.device
+        n = n_timesteps or self.cfg.n_timesteps
+        x = torch.zeros(n_utt, mel, T, dtype=torch.float32, device=dev)
+        mu = torch.zeros(n_utt, mel, T, dtype=torch.float32, device=dev)
+        cond = torch.zeros(n_utt, mel, T, dtype=torch.float32, device=dev)
+        for i in range(n_utt):
+            x[i, :, :lens[i]] = self.rand_noise[0, :, :lens[i]]
+            mu[i, :, :lens[i]] = mus[i]
+            cond[i, :, :lens[i]] = conds[i]
+        spk = torch.stack([s_.to(dev, torch.float32).view(-1) for s_ in spks]).contiguous() if n_utt else torch.zeros(0, mel, device=dev)
+        tl, cov, pa, ld, fill = mel_append_block(lens, covered, caches, cache_fill)
+        ts, dts = euler_schedule(n)
+        ta = (C.c_float * n)(*ts)
+        da = (C.c_float * n)(*dts)
+        ws = self._workspace(2 * max(n_utt, 1), max(T, 1))
+        # (equal lengths: no key-padding masks, as solve_batch and the single-session solve run them)
+        check(self.lib.hvx_cfm_solve_stream_batch(self._h, stream_ptr(), ptr(ws), ws.numel(), n_utt, T, None if not lens or min(lens) == T else tl, ptr(x), ptr(mu),
+                                                  ptr(spk), ptr(cond), n, ta, da, self.static_chunk_size if flags and flags[0] else 0, cov, pa, ld, fill),
+              'hvx_cfm_solve_stream_batch')
+        return [lens[i] - int(covered[i]) for i in range(n_utt)]
+
     @torch.inference_mode()
     def inference_batch(self, tokens, embeddings, prompt_tokens=None, prompt_feats=None, streaming=False):
         """Several utterances through ONE solve (length-bucketed acoustic batches; the reference's `inference` asserts

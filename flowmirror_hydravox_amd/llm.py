@@ -323,14 +323,14 @@ class HvxLLM:
         """Generator over the tokens of request 0 (stream_first) that drives all requests to completion, every request in its own slot."""
         eng = _DecodeEngine(self, n_slots=len(reqs), max_out=max(max(r.max_len for r in reqs), 1), max_prefix=max(len(r.prefix) for r in reqs),
                             stream_first=stream_first, sync_every=sync_every)
-        for kind, x in eng.run(iter(reqs)):
-            if kind == 'token':
-                yield x
+        for ev in eng.run(iter(reqs)):
+            if ev[0] == 'token':
+                yield ev[1]
         self.last_stats = eng.stats
 
     @torch.inference_mode()
     def generate_stream(self, requests, n_slots=None, max_out=None, max_prefix=None, pace=None, mixed_sampling=False, win_cap=None,
-                        mixed_heads=False, head_cap=None):
+                        mixed_heads=False, head_cap=None, stream_tokens=False, sync_every=None):
         """Continuous batching (replaces the one-request-at-a-time loop of server/worker.py:54-102): `requests` is an
         iterable of dicts (text, prompt_text, prompt_speech_token, seed, max_token_text_ratio, min_token_text_ratio, tag).  Up to `n_slots`
         sequences share one decode grid — the weights are streamed once per step for all of them — and the slot of a finished sequence is
@@ -344,7 +344,11 @@ class HvxLLM:
         mixed_heads: the head count is per-sequence state of the grid as well — a request dict may carry `inference_head_num` (effective count
         min(n, head_num), <= 0 -> 1, as the reference; without the key the request takes `llm.inference_head_num`).  The grid is built with
         `head_cap` rows per sequence (default: the model's head_num); every step computes only as many MTP heads as the widest request in
-        flight uses.  A count above `head_cap` comes back as that request's error.  Independent of mixed_sampling; both may be on."""
+        flight uses.  A count above `head_cap` comes back as that request's error.  Independent of mixed_sampling; both may be on.
+        stream_tokens: yields (tag, new ids, False) for every request whenever a host round trip (`sync_every` decode steps, default 8) surfaced ids of it,
+        and (tag, token list | exception, True) when it is complete — the concatenated increments ARE that list, and the list is the one the switch off
+        gives: the same launches, only more is read back.  Composes with mixed_sampling / mixed_heads.  A smaller `sync_every` gives a finer cadence
+        for more host round trips."""
         n_slots = n_slots or self.max_batch
 
         def to_req(d):
@@ -379,13 +383,18 @@ class HvxLLM:
                 max_prefix = max([len(r.prefix) for r in it] + [1])
                 it = iter(it)
         eng = _DecodeEngine(self, n_slots=n_slots, max_out=max_out, max_prefix=max_prefix, pace=pace, mixed_sampling=mixed_sampling, win_cap=win_cap,
-                            **(dict(mixed_heads=True, head_cap=head_cap) if mixed_heads else {}))
+                            **(dict(mixed_heads=True, head_cap=head_cap) if mixed_heads else {}),
+                            **(dict(stream_tokens=True) if stream_tokens else {}), **(dict(sync_every=sync_every) if sync_every else {}))
         gen = eng.run(it)
         try:
-            for kind, r in gen:
-                if kind == 'done':
+            for ev in gen:
+                if ev[0] == 'done':
+                    r = ev[1]
                     # a request that could not run (context / output budget) comes back as (tag, the exception); the others keep running
-                    yield r.tag, (r.out if getattr(r, 'error', None) is None else r.error)
+                    res = r.out if getattr(r, 'error', None) is None else r.error
+                    yield (r.tag, res, True) if stream_tokens else (r.tag, res)
+                elif ev[0] == 'tokens' and stream_tokens:
+                    yield ev[1], ev[2], False
         finally:
             gen.close()                               # an abandoned stream: the engine drains its queued blocks and rewinds the generators
         self.last_stats = eng.stats
@@ -438,8 +447,10 @@ class _DecodeEngine:
     MIXED_WIN_CAP = 64             # default ring capacity of a mixed-sampling grid (the sampler's LDS snapshot holds 256 entries: anything up to that stays on its fast path)
 
     def __init__(self, llm, n_slots, max_out, max_prefix, stream_first=False, sync_every=None, pace=None, mixed_sampling=False, win_cap=None,
-                 mixed_heads=False, head_cap=None):
+                 mixed_heads=False, head_cap=None, stream_tokens=False):
         import time
+        # stream_tokens: stream_first for EVERY slot — after each block the ids of all slots come back in one copy and run() hands out ('tokens', tag, ids)
+        self.stream_tokens = bool(stream_tokens)
         self.mixed = bool(mixed_sampling)
         self.mixed_heads = bool(mixed_heads)
         if not self.mixed_heads and head_cap is not None:
@@ -668,15 +679,18 @@ class _DecodeEngine:
         self.last_fill[i] = launched
         r.state = [n, 0, 0, r.min_len, r.max_len, 0, 0, 0]
         r.cursor = 0
+        r.emitted = 0                            # ids already handed out as ('tokens', ...) (stream_tokens)
 
     def run(self, requests):
-        """generator: ('token', id) for the first request when stream_first, ('done', request) as requests finish"""
+        """generator: ('token', id) for the first request when stream_first, ('tokens', tag, [ids]) for every request as its ids surface when
+        stream_tokens (the ids a block added, before any ('done', ...) that block causes), ('done', request) as requests finish"""
         import time
         llm, S, K, NS, sync_every, stream = self.llm, self.S, self.K, self.NS, self.sync_every, self.stream
         dev = llm.device
         o_state = self.o_state
         slots = [dict(state=torch.zeros(S, 8, dtype=torch.int32).pin_memory(), cur=torch.zeros(S, dtype=torch.int64).pin_memory(),
-                      first=torch.zeros(self.max_out, dtype=torch.int32).pin_memory() if self.stream_first else None, done=torch.cuda.Event())
+                      first=torch.zeros(self.max_out, dtype=torch.int32).pin_memory() if self.stream_first else None,
+                      ids=torch.zeros(S, self.max_out, dtype=torch.int32).pin_memory() if self.stream_tokens else None, done=torch.cuda.Event())
                  for _ in range(NS)]
         blocks = []                                   # (event, event, active sequences, cached positions) per block of steps
         pending_out = []                              # (event, pinned tokens, request) of finished sequences whose ids are on their way
@@ -740,6 +754,10 @@ class _DecodeEngine:
                 slot['cur'].copy_(self.cur_dev, non_blocking=True)
                 if self.stream_first:
                     slot['first'].copy_(self.out_dev[0], non_blocking=True)
+                if self.stream_tokens:
+                    # every slot's ids in ONE contiguous copy into one pinned buffer (S x max_out int32: microseconds beside a block of decode steps); the
+                    # host cuts each slot's new ids out of it with the counts of the state words copied above.  Nothing else is launched.
+                    slot['ids'].copy_(self.out_dev, non_blocking=True)
                 slot['done'].record(stream)
 
         def steps_needed(r):
@@ -869,6 +887,10 @@ class _DecodeEngine:
                         if r is None or r.done or blk < self.join_block[i]:
                             continue                  # empty slot, or a snapshot taken before this request joined
                         r.state, r.cursor = st[i], cursors[i]
+                        if self.stream_tokens and st[i][1] > r.emitted:
+                            # (out_tokens holds accepted ids only: the -1 / -3 a head writes for "nothing accepted" / "not run" stay in the step's id block)
+                            ready.append(('tokens', getattr(r, 'tag', None), cur['ids'][i, r.emitted:st[i][1]].tolist()))
+                            r.emitted = st[i][1]
                         if st[i][6] == 1:
                             raise RuntimeError('sampling reaches max_trials {} and still get eos when ignore_eos is True, check your input!'.format(self.max_trials))
                         if st[i][2]:                  # finished: fetch its ids; the slot is free for the next request from here on

@@ -298,3 +298,28 @@ def resample_sinc(x, taps_dev, orig, new, width):
     check(lib.hvx_op_resample_sinc(ptr(x), rows, L, x.stride(0) if rows > 1 else L, ptr(taps_dev), orig, new, width, ptr(out), out.shape[1], out.shape[1],
                                    stream_ptr()), 'hvx_op_resample_sinc')
     return out
+
+
+def mel_append_block(t_len, covered, caches, cache_fill):
+    """the host argument arrays of hvx_op_mel_cache_append / hvx_cfm_solve_stream_batch for cache planes `caches` (each a contiguous fp32 (mel, ld_i) tensor):
+    (t_len, covered, cache pointers, cache_ld, cache_fill) as ctypes arrays"""
+    n = len(caches)
+    if not (len(t_len) == len(covered) == len(cache_fill) == n):
+        raise ValueError('t_len, covered, caches and cache_fill must have one entry per session')
+    for c in caches:
+        assert c.dim() == 2 and c.dtype == torch.float32 and c.is_contiguous(), (c.shape, c.dtype, c.stride())
+    ia = lambda v: (C.c_int32 * max(n, 1))(*[int(x) for x in v])
+    pa = (C.c_void_p * max(n, 1))(*[c.data_ptr() for c in caches])
+    return ia(t_len), ia(covered), pa, ia([c.shape[1] for c in caches]), ia(cache_fill)
+
+
+def mel_cache_append(x, t_len, covered, caches, cache_fill):
+    """Frames [covered[i], t_len[i]) of all mel rows of x[i] — x a float32 (n, mel, t_max) device tensor — are copied into session i's cache plane `caches[i]`
+    ((mel, ld_i) float32, contiguous) from column cache_fill[i] on; nothing else of a plane is touched.  An append that would overflow its plane,
+    covered[i] > t_len[i] or no session at all raises HvxError before anything is launched.  csrc/elementwise.hip: mel_cache_append_kernel."""
+    lib = _lib.load()
+    assert x.dim() == 3 and x.dtype == torch.float32 and x.is_contiguous(), (x.shape, x.dtype)
+    if x.shape[0] != len(caches):
+        raise ValueError('x holds %d sessions, %d cache planes given' % (x.shape[0], len(caches)))
+    tl, cov, pa, ld, fill = mel_append_block(t_len, covered, caches, cache_fill)
+    check(lib.hvx_op_mel_cache_append(ptr(x), len(caches), x.shape[1], x.shape[2], tl, cov, pa, ld, fill, stream_ptr()), 'hvx_op_mel_cache_append')

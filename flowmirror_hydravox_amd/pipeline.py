@@ -76,6 +76,54 @@ def _flow_prompt(u):
     return u.prompt_speech_token if u.flow_prompt_token is None else u.flow_prompt_token
 
 
+class _HostStream:
+    """the acoustic "stream" of a pipeline over host stand-in models (from_models with objects on the CPU: the scheduling tests) — nothing to order or wait for"""
+    device = torch.device('cpu')
+
+    def synchronize(self):
+        pass
+
+
+def _on(stream):
+    import contextlib
+    return contextlib.nullcontext() if isinstance(stream, _HostStream) else torch.cuda.stream(stream)
+
+
+class _StreamUtterance:
+    """One utterance of `serve(stream=True)` between its first token and its last piece: what `streaming.StreamSession` keeps for a single request,
+    as state the batched acoustic stage can work on — the mel cache plane (sized from the utterance's token budget; `fill` frames are valid), the chunk
+    schedule, the prompt arguments of the flow, the jobs that are ready and `handed`, the samples already handed out."""
+
+    def __init__(self, u, flow, hop, max_tokens, device, t_fetch):
+        from .streaming import ChunkSchedule
+        pt = _flow_prompt(u)
+        self.u = u
+        self.prompt_token = None if pt is None else pt.reshape(-1).to(device, torch.int32)
+        self.prompt_feat = None if u.prompt_feat is None else u.prompt_feat.reshape(-1, flow.output_size).to(device, torch.float32)
+        self.embedding = u.embedding.to(device)
+        self.n_prompt = 0 if self.prompt_token is None else int(self.prompt_token.numel())
+        self.prompt_frames = 0 if self.prompt_feat is None else int(self.prompt_feat.shape[0])
+        self.sched = ChunkSchedule(self.n_prompt, hop, flow.pre_lookahead_len)
+        self.cache = torch.empty(flow.output_size, max(1, int(max_tokens)) * flow.token_mel_ratio, dtype=torch.float32, device=device)
+        self.fill = 0
+        self.handed = 0
+        self.jobs = []                   # (tokens in the piece, covered, final) not yet solved, in order
+        self.pieces = 0
+        self.tokens = None               # the utterance's full token list, once the LM has finished it
+        self.t_fetch = t_fetch
+
+    def flow_inputs(self, flow, n, final):
+        """mu, spk, cond of the flow over the prompt and the first n generated tokens (HvxFlow.inference's plumbing)"""
+        tok = torch.tensor(self.sched.tokens[:n], dtype=torch.int32, device=self.cache.device)
+        if self.prompt_token is not None:
+            tok = torch.concat([self.prompt_token, tok])
+        mu, spk = flow.encode(tok, self.embedding.reshape(-1), finalize=final)
+        cond = torch.zeros(flow.output_size, mu.shape[-1], dtype=torch.float32, device=self.cache.device)
+        if self.prompt_feat is not None:
+            cond[:, :self.prompt_frames] = self.prompt_feat.t()
+        return mu, spk, cond
+
+
 class HvxPipeline:
     def __init__(self, cfg: HvxConfig, llm_sd=None, flow_sd=None, hift_sd=None, llm_dtype=torch.bfloat16, flow_dtype=torch.bfloat16,
                  device='cuda', max_batch=8, max_ctx=4096, max_t=None, seed=1986, init='normal02', hift_tables=None, sampling=None,
@@ -287,7 +335,8 @@ class HvxPipeline:
 
     @torch.inference_mode()
     def serve(self, source, lm_slots=16, acoustic_batch=None, acoustic_min_batch=1, max_out=None, max_prefix=None,
-              max_token_text_ratio=20, min_token_text_ratio=2, pace=None, mixed_sampling=False, win_cap=None, mixed_heads=False, head_cap=None):
+              max_token_text_ratio=20, min_token_text_ratio=2, pace=None, mixed_sampling=False, win_cap=None, mixed_heads=False, head_cap=None,
+              stream=False, sync_every=None, event_log=None):
         """The continuous engine over an open-ended SOURCE of utterances: `source.poll(block)` returns the next `Utterance`, or None when
         nothing is waiting (it is asked to block only while the decode grid is idle), and raises StopIteration when closed.  Generator over
         (utterance, waveform | exception, tokens) in completion order.
@@ -304,14 +353,32 @@ class HvxPipeline:
         `pace` = (first, every_steps, more): admission pacing of the decode grid (see _DecodeEngine.run).
         `mixed_sampling`: utterances may carry their own `sampling` and decode side by side with others' (HvxLLM.generate_stream; `win_cap` is
         the longest repetition window the grid holds).  Off, an utterance that carries `sampling` comes back with an error.
-        `mixed_heads`: the same for `inference_head_num` (`head_cap`: rows per sequence of the grid, default the model's head_num)."""
+        `mixed_heads`: the same for `inference_head_num` (`head_cap`: rows per sequence of the grid, default the model's head_num).
+        `stream`: audio leaves in PIECES while the utterances are still decoding — the reference's chunked synthesis (streaming.stream_tts) for every
+        utterance of the grid at once.  The generator then yields (utterance, piece, info) for every piece of every utterance in the order the pieces
+        become ready, interleaved across utterances; info = {'index': piece number from 0, 'final': bool} and, on the final piece, 'tokens': the
+        utterance's token list.  Pieces of one utterance come in order and concatenate to its audio.  The LM hands over the ids of every slot after each
+        host round trip (generate_stream(stream_tokens=True)), a `ChunkSchedule` per utterance says when a chunk is ready, and the ready chunks of different
+        utterances — up to `acoustic_batch`, in the length buckets of the unstreamed path — share one chunk-masked solve over their token prefixes
+        (HvxFlow.solve_stream_batch) that appends the new frames to each utterance's mel cache; the vocoder runs per utterance over its cache.  An
+        utterance with speed != 1.0 comes back as (utterance, AssertionError, {}): the reference refuses it too.  `acoustic_min_batch` does not apply.
+        The mel cache of an utterance holds `max_out` tokens when that is given, otherwise the utterance's own token budget (its text length x its
+        `max_token_text_ratio`, or this call's).  self.last_continuous gains `pieces`, `chunk_solves`, `first_piece_seconds` ((n, seconds from the
+        utterance's fetch to its first piece) of the latest 4096 utterances, n = fetch order) and `pieces_out` (pieces already handed out, per entry of
+        `abandoned`).  `event_log`: a list (or anything with append) that receives the engine's log as it happens — ('tokens', n, count) / ('done', n)
+        from the LM thread, ('piece', n, index, final) from this one; nothing is logged without it (a server's serve() call may live for days).
+        `sync_every`: decode steps per host round trip of the grid (default 8); smaller: tokens — and so pieces — surface at a finer cadence, for more
+        round trips."""
         acoustic_batch = acoustic_batch or self.acoustic_batch
         acoustic_min_batch = max(1, min(int(acoustic_min_batch), acoustic_batch))
+        piecewise = bool(stream)                           # (`stream` names the acoustic stage's device stream below)
         import queue
         import threading
         if getattr(self, '_bg_stream', None) is None:
             lm_cus = int(getattr(self, 'lm_cus', 0) or 0)
-            if lm_cus > 0:
+            if self.device.type != 'cuda':
+                self._bg_stream = _HostStream()
+            elif lm_cus > 0:
                 # CU partition (docs/history/DESIGN_rounds1-4.md §5.0): the decode engine on CUs [0, lm_cus), the acoustic stage on the rest — both ranges spread over all
                 # 8 XCDs.  Must be set before the first decode engine of self.llm is built (the engine keeps its stream).
                 from . import _lib
@@ -332,15 +399,25 @@ class HvxPipeline:
             self._bg_streams = [self._bg_stream]
             self._bg_pools = []
         flow, hift, stream = self._acoustic_chain(0)
-        torch.cuda.synchronize(self.device)               # (everything the handles were built from is complete before other streams use it)
+        if self.device.type == 'cuda':
+            torch.cuda.synchronize(self.device)           # (everything the handles were built from is complete before other streams use it)
         # bounded, but wide enough that a whole grid can finish at once without the decode engine waiting on this queue (it stalls inside its
         # `yield` while the LM thread is blocked in put): only a consumer that has fallen a full grid behind holds the LM back
-        q = queue.Queue(maxsize=2 * int(lm_slots) + 2 * acoustic_batch)
+        q_len = 2 * int(lm_slots) + 2 * acoustic_batch
+        if piecewise:
+            # ... which, streamed, also takes room for the token items: every slot puts one per block of `sync_every` steps (at least one id each), so
+            # a whole grid's worth of them is lm_slots * max_out / sync_every; the items are short id lists
+            q_len += int(lm_slots) * (-(-int(max_out or getattr(self.llm, 'max_ctx', 4096)) // int(sync_every or 8)))
+        q = queue.Queue(maxsize=q_len)
         cancel = threading.Event()
         lm_info = {}
         seen = {}                                          # running id -> utterance in flight; an entry goes when its result is handed out
         n_seen = [0]
         abandoned = []                                     # fetched from a source without `unpoll` while the engine was being cancelled
+        from collections import deque
+        fetched = {}                                       # stream: running id -> (time of its fetch, tokens its mel cache must hold), until its session exists
+        live = {}                                          # stream: running id -> _StreamUtterance, until its final piece has left
+        acct = dict(pieces=0, chunk_solves=0, first=deque(maxlen=4096), acoustic=0.0, audio=0.0, tokens=0)
 
         class _Requests:
             @staticmethod
@@ -350,18 +427,27 @@ class HvxPipeline:
                 # within that bound instead of when the next request happens to arrive.
                 if cancel.is_set():
                     raise StopIteration
-                u = source.poll(block)
-                if u is None:
-                    return None
-                if cancel.is_set():                        # fetched while the engine was being cancelled: hand it back rather than fail it
-                    if hasattr(source, 'unpoll'):
-                        source.unpoll(u)
-                    else:                                  # (a source without `unpoll`: it is reported with the abandoned ones, never silently lost)
-                        abandoned.append(u)
-                    raise StopIteration
-                tag = n_seen[0]
-                n_seen[0] += 1
-                seen[tag] = u
+                while True:
+                    u = source.poll(block)
+                    if u is None:
+                        return None
+                    if cancel.is_set():                    # fetched while the engine was being cancelled: hand it back rather than fail it
+                        if hasattr(source, 'unpoll'):
+                            source.unpoll(u)
+                        else:                              # (a source without `unpoll`: it is reported with the abandoned ones, never silently lost)
+                            abandoned.append(u)
+                        raise StopIteration
+                    tag = n_seen[0]
+                    n_seen[0] += 1
+                    seen[tag] = u
+                    if piecewise and u.speed != 1.0:          # (cosyvoice/cli/model.py:425) answered at once, it never takes a slot
+                        if not put((tag, AssertionError('speed change only support non-stream inference mode'), True)):
+                            raise StopIteration
+                        continue
+                    break
+                if piecewise:
+                    budget = max_out if max_out is not None else int(len(u.text) * (max_token_text_ratio if u.max_token_text_ratio is None else u.max_token_text_ratio))
+                    fetched[tag] = (time.time(), max(int(budget), 1))
                 return dict(text=u.text, prompt_text=u.prompt_text, prompt_speech_token=u.prompt_speech_token, seed=u.seed, tag=tag, sampling=u.sampling,
                             inference_head_num=u.inference_head_num,
                             max_token_text_ratio=max_token_text_ratio if u.max_token_text_ratio is None else u.max_token_text_ratio,
@@ -378,15 +464,19 @@ class HvxPipeline:
 
         def lm_thread():
             try:
-                torch.cuda.set_device(stream.device)               # the current device is per thread
+                if self.device.type == 'cuda':
+                    torch.cuda.set_device(stream.device)           # the current device is per thread
                 with torch.inference_mode():
                     t0 = time.time()
                     gen = self.llm.generate_stream(_Requests(), n_slots=lm_slots, max_out=max_out, max_prefix=max_prefix, pace=pace,
                                                    **(dict(mixed_sampling=True, win_cap=win_cap) if mixed_sampling else {}),
-                                                   **(dict(mixed_heads=True, head_cap=head_cap) if mixed_heads else {}))
+                                                   **(dict(mixed_heads=True, head_cap=head_cap) if mixed_heads else {}),
+                                                   **(dict(stream_tokens=True) if piecewise else {}), **(dict(sync_every=sync_every) if sync_every else {}))
                     try:
-                        for tag, toks in gen:
-                            if not put((tag, toks)):
+                        for item in gen:
+                            if piecewise and event_log is not None:
+                                event_log.append(('done', item[0]) if item[2] else ('tokens', item[0], len(item[1])))
+                            if not put(item):
                                 break
                     finally:
                         gen.close()
@@ -401,7 +491,9 @@ class HvxPipeline:
         acoustic = audio = 0.0
         tokens = 0
         try:
-            while True:
+            if piecewise:
+                yield from self._stream_consumer(q, seen, fetched, live, flow, hift, stream, acoustic_batch, acct, event_log)
+            while not piecewise:
                 item = q.get()
                 if item is None:
                     break
@@ -425,7 +517,7 @@ class HvxPipeline:
                 if group:
                     us = [seen[i] for i, _ in group]
                     t0 = time.time()
-                    with torch.cuda.stream(stream):
+                    with _on(stream):
                         wavs = self._waves(self._mels_batched(us, [t for _, t in group], flow, max_batch=acoustic_batch), hift, speeds=[u.speed for u in us])
                         stream.synchronize()
                     acoustic += time.time() - t0
@@ -448,6 +540,124 @@ class HvxPipeline:
             self.last_continuous = dict(tokens=tokens, audio_seconds=audio, acoustic_seconds=acoustic, total_seconds=time.time() - t_begin,
                                         llm_seconds=lm_info.get('seconds', 0.0), llm=lm_info.get('stats', {}), lm_slots=lm_slots,
                                         abandoned=abandoned + list(seen.values()))
+            if piecewise:
+                self.last_continuous.update(tokens=acct['tokens'], audio_seconds=acct['audio'], acoustic_seconds=acct['acoustic'], pieces=acct['pieces'],
+                                            chunk_solves=acct['chunk_solves'], first_piece_seconds=list(acct['first']),
+                                            pieces_out=[0] * len(abandoned) + [live[k].pieces if k in live else 0 for k in seen])
+
+    def _stream_consumer(self, q, seen, fetched, live, flow, hift, stream, acoustic_batch, acct, event_log, max_pad=0.15):
+        """the acoustic stage of serve(stream=True): generator over (utterance, piece | exception, info).  Queue items are generate_stream(stream_tokens=True)'s:
+        (n, new ids, False) and (n, token list | exception, True), None when the LM is done.  `live`: n -> _StreamUtterance (serve reads it when it ends)."""
+        import queue
+        hop = flow.static_chunk_size // flow.token_mel_ratio        # "must matching training static_chunk_size" (cosyvoice/cli/model.py:395-396)
+        ratio = flow.token_mel_ratio
+        order = []                                                 # n of every job that is ready, oldest first
+        ended = False
+
+        def session(n):
+            if n not in live:
+                t_fetch, budget = fetched.pop(n)
+                with _on(stream):                                  # (its copies to the device are ordered with the solves that read them)
+                    live[n] = _StreamUtterance(seen[n], flow, hop, budget, self.device, t_fetch)
+            return live[n]
+
+        def drop(n):
+            """utterance n leaves without (further) pieces: its session, its bookkeeping and whatever of it was scheduled"""
+            live.pop(n, None)
+            fetched.pop(n, None)
+            order[:] = [m for m in order if m != n]
+
+        def log(*ev):
+            if event_log is not None:
+                event_log.append(ev)
+        while True:
+            # ---- everything the LM has handed over so far; wait only when no chunk is ready
+            while not ended:
+                try:
+                    item = q.get_nowait() if order else q.get()
+                except queue.Empty:
+                    break
+                if item is None:
+                    ended = True
+                    break
+                if isinstance(item, BaseException):
+                    raise item
+                n, ids, done = item
+                if not done:
+                    se = session(n)
+                    for k, covered in se.sched.feed(ids):
+                        se.jobs.append((k, covered, False))
+                        order.append(n)
+                elif isinstance(ids, BaseException):
+                    drop(n)
+                    yield seen.pop(n), ids, {}
+                elif not ids:                                      # nothing was generated: one empty, final piece
+                    drop(n)
+                    log('piece', n, 0, True)
+                    acct['pieces'] += 1
+                    yield seen.pop(n), torch.zeros(0, device=self.device), dict(index=0, final=True, tokens=[])
+                else:
+                    se = session(n)
+                    for k, covered in se.sched.feed(ids[len(se.sched.tokens):]):      # (every id has come as an increment already; an LM that sends none is served too)
+                        se.jobs.append((k, covered, False))
+                        order.append(n)
+                    k, covered = se.sched.finish()
+                    se.tokens = list(ids)
+                    se.jobs.append((k, covered, True))
+                    order.append(n)
+            if not order:
+                if ended:
+                    return
+                continue
+            # ---- one job each of up to `acoustic_batch` utterances, oldest first (the jobs of ONE utterance follow each other: each appends to its cache)
+            picked, rest = [], []
+            for n in order:
+                if len(picked) < acoustic_batch and n not in picked:
+                    picked.append(n)
+                else:
+                    rest.append(n)
+            order = rest
+            jobs = {n: live[n].jobs.pop(0) for n in picked}
+            t0 = time.time()
+            out = []
+            with _on(stream):
+                for final in (False, True):                        # a final job runs with the full mask: its own solves
+                    todo = sorted((n for n in picked if jobs[n][2] == final), key=lambda n: -(live[n].n_prompt + jobs[n][0]))
+                    while todo:
+                        top = live[todo[0]].n_prompt + jobs[todo[0]][0]
+                        bucket = [n for n in todo if live[n].n_prompt + jobs[n][0] >= (1.0 - max_pad) * top]
+                        todo = [n for n in todo if n not in bucket]
+                        ins = [live[n].flow_inputs(flow, jobs[n][0], final) for n in bucket]
+                        fresh = flow.solve_stream_batch([i[0] for i in ins], [i[1] for i in ins], [i[2] for i in ins],
+                                                        [live[n].prompt_frames + jobs[n][1] * ratio for n in bucket], [live[n].cache for n in bucket],
+                                                        [live[n].fill for n in bucket], streaming=not final)
+                        acct['chunk_solves'] += 1
+                        for n, f in zip(bucket, fresh):
+                            se = live[n]
+                            se.fill += f
+                            wav, _ = hift.inference(speech_feat=se.cache[None, :, :se.fill], finalize=final)
+                            piece = wav[0, se.handed:]
+                            se.handed += piece.numel()
+                            out.append((n, piece, final))
+                stream.synchronize()
+            acct['acoustic'] += time.time() - t0
+            for n, piece, final in sorted(out, key=lambda o: picked.index(o[0])):
+                se = live[n]
+                info = dict(index=se.pieces, final=final)
+                if se.pieces == 0:
+                    acct['first'].append((n, time.time() - se.t_fetch))
+                se.pieces += 1
+                acct['pieces'] += 1
+                acct['audio'] += piece.numel() / float(self.cfg.sample_rate)
+                log('piece', n, info['index'], final)
+                if final:
+                    info['tokens'] = se.tokens
+                    acct['tokens'] += len(se.tokens)
+                    del live[n]
+                    u = seen.pop(n)
+                else:
+                    u = seen[n]
+                yield u, piece, info
 
     @torch.inference_mode()
     def synthesize_pipelined(self, batches, max_token_text_ratio=20, min_token_text_ratio=2, lm_chains=3, acoustic_chains=1):

@@ -61,36 +61,58 @@ class StreamSession:
         return self.push(token, token_offset, stream=stream, finalize=finalize, speed=speed)
 
 
+class ChunkSchedule:
+    """The chunk schedule of the reference's `tts(stream=True)` (cli/model.py:329-352) as host state of one utterance: which token prefixes go through the
+    flow, and how many of their tokens earlier passes already covered.  A job is `(n_tokens_in_piece, covered)`: the flow runs over the first
+    `n_tokens_in_piece` generated tokens (the last `pre_lookahead_len` of them are look-ahead only) and the frames past `covered` tokens are new.
+    The first hop is padded so that prompt + hop is a whole number of `token_hop_len` chunks (`prompt_token_pad`), a job is ready as soon as
+    hop + look-ahead unseen tokens are buffered, and `finish()` gives the last job: every token, full mask, `finalize=True`."""
+
+    def __init__(self, n_prompt_tokens, token_hop_len, pre_lookahead_len):
+        self.hop_len, self.look = int(token_hop_len), int(pre_lookahead_len)
+        self.prompt_token_pad = int(math.ceil(n_prompt_tokens / self.hop_len) * self.hop_len - n_prompt_tokens)
+        self.tokens = []
+        self.covered = 0                 # the reference's token_offset
+        self.finished = False
+
+    def _hop(self):
+        return self.hop_len + self.prompt_token_pad if self.covered == 0 else self.hop_len
+
+    def feed(self, ids):
+        """more generated ids (any number, also none) -> the jobs that became ready, in order"""
+        assert not self.finished
+        jobs = []
+        for t in ids:
+            self.tokens.append(int(t))
+            hop = self._hop()                                    # (looked at after every token, as the reference's loop does: at most one job per token)
+            if len(self.tokens) - self.covered >= hop + self.look:
+                jobs.append((self.covered + hop + self.look, self.covered))
+                self.covered += hop
+        return jobs
+
+    def finish(self):
+        """the LM has stopped: the job of the final pass (whatever remains, full attention mask, finalize=True)"""
+        self.finished = True
+        return len(self.tokens), self.covered
+
+
 def stream_tts(token_source, flow, hift, prompt_token, prompt_feat, embedding, token_hop_len=25, stream=True, speed=1.0):
     """Generator of waveform pieces (1, L) float32 from an iterable of speech-token ids (e.g. `HvxLLM.inference(...)`).
 
-    The chunk schedule is the reference's (cli/model.py:329-352): the first hop is padded so that prompt + hop is a whole number
+    The chunk schedule is the reference's (cli/model.py:329-352), kept in `ChunkSchedule`: the first hop is padded so that prompt + hop is a whole number
     of `token_hop_len` chunks (`prompt_token_pad`), a chunk is synthesised as soon as `hop + pre_lookahead_len` unseen tokens are
     buffered, and whatever remains when the LM stops goes through once more with `finalize=True`.  `token_hop_len` must be
     `static_chunk_size / token_mel_ratio` ("must matching training static_chunk_size", cli/model.py:395-396).
     """
     sess = StreamSession(flow, hift, prompt_token, prompt_feat, embedding)
-    tokens = []
     if not stream:
         tokens = [int(t) for t in token_source]
         yield sess.token2wav(torch.tensor(tokens, dtype=torch.int32).unsqueeze(0), 0, stream=False, finalize=True, speed=speed)
         return
-    look = flow.pre_lookahead_len
-    n_prompt = prompt_token.shape[1]
-    prompt_token_pad = int(math.ceil(n_prompt / token_hop_len) * token_hop_len - n_prompt)
-    token_offset = 0
-
-    def ready():
-        hop = token_hop_len + prompt_token_pad if token_offset == 0 else token_hop_len
-        return hop, len(tokens) - token_offset >= hop + look
-
+    sched = ChunkSchedule(prompt_token.shape[1], token_hop_len, flow.pre_lookahead_len)
     for t in token_source:
-        tokens.append(int(t))
-        hop, ok = ready()
-        if ok:
-            piece = torch.tensor(tokens[:token_offset + hop + look], dtype=torch.int32).unsqueeze(0)
-            wav = sess.token2wav(piece, token_offset, stream=True, finalize=False)
-            token_offset += hop
-            yield wav
+        for n, covered in sched.feed([t]):
+            yield sess.token2wav(torch.tensor(sched.tokens[:n], dtype=torch.int32).unsqueeze(0), covered, stream=True, finalize=False)
     # the reference's last call leaves `stream` at its default False (cli/model.py:355-361): the final pass uses the full attention mask
-    yield sess.token2wav(torch.tensor(tokens, dtype=torch.int32).unsqueeze(0), token_offset, stream=False, finalize=True)
+    n, covered = sched.finish()
+    yield sess.token2wav(torch.tensor(sched.tokens[:n], dtype=torch.int32).unsqueeze(0), covered, stream=False, finalize=True)

@@ -213,7 +213,7 @@ class _TaskSource:
 
 
 def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_id, frontend_factory=None, lm_slots=None, acoustic_batch=4,
-                               mixed_sampling=False, mixed_heads=False):
+                               mixed_sampling=False, mixed_heads=False, stream=False):
     """Same wire format as worker_process_tts, served by the continuous-batching engine (replaces the one-request-at-a-time
     loop of server/worker.py:54-102 and what server/router.py:144-156 feeds it): `tts` / `zero_shot` tasks join ONE decode grid as they arrive
     (HvxPipeline.serve -> HvxLLM.generate_stream: the LM weights are streamed once per step for every request in flight, a finished request's
@@ -222,7 +222,8 @@ def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_
     are epoch boundaries (FIFO: see _TaskSource).  What bench.py measures is this path.
     mixed_sampling=True: requests with different top_p / top_k / win_size / tau_r share the grid, each sampling with its own values; only
     another inference_head_num, a window over 64 (or 0) and the non-synthesis tasks remain epoch boundaries.
-    mixed_heads=True: requests with different inference_head_num share the grid as well (rows per sequence: the model's head_num)."""
+    mixed_heads=True: requests with different inference_head_num share the grid as well (rows per sequence: the model's head_num).
+    stream=True: one result message per audio PIECE (see serve_queue)."""
     os.environ['CUDA_VISIBLE_DEVICES'] = str(worker_id % num_workers_gpu)
     from .model_manager import HvxModelManager
     from .pipeline import HvxPipeline
@@ -232,15 +233,18 @@ def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_
     mm.load_models(argparse.Namespace(config=os.getenv('TTS_CONFIG'), model_dir=os.getenv('TTS_MODEL_DIR'), bf16=_env_flag('TTS_BF_16'),
                                       fp16=_env_flag('TTS_FP_16'), cpu=_env_flag('TTS_CPU', False)))
     serve_queue(mm, task_queue, result_dict, worker_id, lm_slots=lm_slots, acoustic_batch=acoustic_batch, mixed_sampling=mixed_sampling,
-                mixed_heads=mixed_heads)
+                mixed_heads=mixed_heads, **(dict(stream=True) if stream else {}))
 
 
 def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acoustic_batch=4, normalise=None, mixed_sampling=False, win_cap=64, token_log=None,
-                mixed_heads=False, head_cap=None):
+                mixed_heads=False, head_cap=None, stream=False):
     """the loop of worker_process_tts_batched over an already loaded model manager (tests drive this directly).  Returns its counters:
     `epochs` (decode grids started) and `epoch_boundaries` (tasks that closed a running grid because they could not join it; the shutdown
     sentinel is not one).  token_log: a dict that receives task id -> speech-token ids of every synthesised request.
-    mixed_heads / head_cap: see _TaskSource; llm.inference_head_num is still written at epoch start only (the first task's)."""
+    mixed_heads / head_cap: see _TaskSource; llm.inference_head_num is still written at epoch start only (the first task's).
+    stream=True: HvxPipeline.serve(stream=True) — every audio piece of a request is a result message of its own, written the moment the piece exists under
+    the key stream_result_key(task id, piece_index): the keys of an unstreamed result (`output_audio` = this piece's samples, `duration` = this piece's) plus
+    `piece_index` and `final`.  A request that fails is answered once, under its task id, as without the switch."""
     stats = dict(epochs=0, epoch_boundaries=0, mixed_sampling=bool(mixed_sampling), mixed_heads=bool(mixed_heads))
     from .pipeline import HvxPipeline
     from .sampling import ras_sampling
@@ -280,8 +284,24 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
             kw = dict(mixed_sampling=True, win_cap=win_cap) if src.mixed else {}
             if src.mixed_heads:
                 kw.update(mixed_heads=True, head_cap=head_cap)
+            if stream:
+                kw.update(stream=True)
             for u, wav, toks in pipe.serve(_Tracked(src, in_flight), lm_slots=lm_slots, acoustic_batch=acoustic_batch, acoustic_min_batch=1, **kw):
                 t = u.tag
+                if stream and not isinstance(wav, BaseException):
+                    info = toks                                 # (utterance, piece, info)
+                    if info['final']:
+                        in_flight.pop(t['id'], None)
+                        if token_log is not None:
+                            token_log[t['id']] = list(info['tokens'])
+                    out = wav.reshape(1, -1).cpu()
+                    msg = {'output_audio': out, 'sample_rate': sr, 'format': 'wav' if t['task_type'] == 'tts' else t.get('output_format', 'wav'),
+                           'duration': out.shape[-1] / sr}
+                    if t['task_type'] == 'tts':
+                        msg.update(speaker_id=getattr(u, 'speaker_id', t.get('speaker_id')), segments_info=None)
+                    msg.update(piece_index=info['index'], final=info['final'])
+                    result_dict[stream_result_key(t['id'], info['index'])] = msg
+                    continue
                 in_flight.pop(t['id'], None)
                 if token_log is not None and not isinstance(wav, BaseException):
                     token_log[t['id']] = list(toks)
@@ -305,6 +325,11 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
         if src.stop:
             break
     return stats
+
+
+def stream_result_key(task_id, piece_index):
+    """where serve_queue(stream=True) puts piece `piece_index` of a task's audio in the result dict"""
+    return '%s:%d' % (task_id, piece_index)
 
 
 class _Tracked:

@@ -425,6 +425,20 @@ int hvx_cfm_solve_batch(hvx_flow* h, hvx_stream s, void* ws, size_t ws_bytes, in
                         const float* mu, const float* spks, const float* cond, int32_t n_steps, const float* t_steps, const float* dt_steps,
                         int32_t static_chunk_size);
 
+/* Chunked synthesis of n streaming sessions in one call (still ABI 7, additive).  hvx_cfm_solve_batch over the sessions' PREFIXES (prompt + every token so far,
+ * re-solved as the reference's token2wav does, cosyvoice/cli/model.py:405-430) with the chunk mask of static_chunk_size (0: the full mask, a session's final pass),
+ * then ONE launch per 16 sessions of mel_cache_append_kernel: frames [covered[i], t_len[i]) of every mel row of x[i] are copied into session i's cache plane
+ * cache[i] — (mel, cache_ld[i]) fp32 — from column cache_fill[i] on.  Frames at or beyond t_len[i] are padding and never reach a cache.
+ * t_len, covered, cache_ld, cache_fill: HOST int32 [n] (t_len may be NULL: every session has t_max frames); cache: HOST array of n device pointers.  Their values
+ * travel to the device by value.  covered[i] > t_len[i], t_len[i] > t_max, cache_fill[i] + t_len[i] - covered[i] > cache_ld[i], a negative entry, a null plane or
+ * n < 1 return -1 before anything is launched.  x, mu, spks, cond, workspace, schedule: as hvx_cfm_solve_batch. */
+int hvx_cfm_solve_stream_batch(hvx_flow* h, hvx_stream s, void* ws, size_t ws_bytes, int32_t n, int32_t t_max, const int32_t* t_len, float* x,
+                               const float* mu, const float* spks, const float* cond, int32_t n_steps, const float* t_steps, const float* dt_steps,
+                               int32_t static_chunk_size, const int32_t* covered, float* const* cache, const int32_t* cache_ld, const int32_t* cache_fill);
+/* the copy alone: x (n, mel, t_max) f32, the per-session arrays as above (host); any n >= 1, split into launches of 16 sessions */
+int hvx_op_mel_cache_append(const float* x, int32_t n, int32_t mel, int32_t t_max, const int32_t* t_len, const int32_t* covered, float* const* cache,
+                            const int32_t* cache_ld, const int32_t* cache_fill, hvx_stream s);
+
 /* ---------------------------------------------------------------------------------------------------
  * HiFT — replaces CausalHiFTGenerator.inference / decode (cosyvoice/hifigan/generator.py:713-726, 672-711),
  * CausalConvRNNF0Predictor.forward (cosyvoice/hifigan/f0_predictor.py:95-103), SourceModuleHnNSF / SineGen2
