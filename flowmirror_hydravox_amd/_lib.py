@@ -195,6 +195,7 @@ SYMBOLS = {
     'hvx_llm_decode_steps_mixed': (c_i32, [c_vp, c_vp, C.POINTER(DecodeArgs), C.POINTER(SeqSampling), C.POINTER(SeqHeads), c_i32, c_i32]),
     'hvx_llm_decode_join_mixed': (c_i32, [c_vp, c_vp, C.POINTER(DecodeArgs), C.POINTER(SeqSampling), C.POINTER(SeqHeads), c_i32, c_i32, c_i32, c_i32, c_i32,
                                           c_i32, c_f32, c_i32, c_i32, c_i32]),
+    'hvx_llm_decode_leave': (c_i32, [c_vp, c_vp, C.POINTER(DecodeArgs), c_i32]),
     'hvx_llm_use_graph': (c_i32, [c_vp, c_i32]),
     'hvx_llm_set_head_mlp_fp8': (c_i32, [c_vp, c_vp, c_vp]),
     'hvx_llm_last_hidden': (c_i32, [c_vp, c_vp, c_i32, c_vp]),
@@ -259,7 +260,7 @@ SYMBOLS = {
 # rebuild command, exactly as a version mismatch would.  The per-sequence sampling entry points (hvx_ras_sample_seq, hvx_llm_decode_steps_seq,
 # hvx_llm_decode_join_seq and their hvx_seq_sampling block) joined the same way: additive, no existing struct or symbol touched; so did the
 # per-sequence head counts (hvx_ras_sample_mixed, hvx_llm_decode_steps_mixed, hvx_llm_decode_join_mixed and hvx_seq_heads), and the streaming batch of the
-# serving engine (hvx_cfm_solve_stream_batch, hvx_op_mel_cache_append).
+# serving engine (hvx_cfm_solve_stream_batch, hvx_op_mel_cache_append), and hvx_llm_decode_leave (a cancelled request's slot is retired on the stream).
 HVX_ABI_VERSION = 7
 
 _lib = None

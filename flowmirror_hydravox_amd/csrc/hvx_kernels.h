@@ -300,6 +300,9 @@ int launch_decode_advance(const AdvanceArgs& a, hipStream_t s);
 int launch_decode_join(const AdvanceArgs& a, long long* cursor, int slot, int first_tok, int pos, int min_len, int max_len, hipStream_t s,
                        const SeqSampling* q = nullptr, int heads = 0);      // heads > 0: the slot's head count, written to a.seq_heads[slot]
 
+// the caller retires slot `slot` (a cancelled request): uses n_seq, head_k, tok, ctrl, active and seq_state of `a` only
+int launch_decode_leave(const AdvanceArgs& a, int slot, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------
 // HiFT source / STFT / iSTFT
 // ------------------------------------------------------------------------------------------------

@@ -407,6 +407,18 @@ int hvx_llm_decode_join_mixed(hvx_llm* h, hvx_stream stream, const hvx_decode_ar
     return decode_join_impl(h, stream, a, q, &v, slot, first_tok, pos, min_len, max_len, heads, head_k);
 }
 
+int hvx_llm_decode_leave(hvx_llm* h, hvx_stream stream, const hvx_decode_args* a, int32_t slot) {
+    if (!h || !h->ws || !a) return set_error("hvx_llm_decode_leave: handle not bound / null argument"), -1;
+    if (a->n_seq < 1 || a->head_k < 1 || a->head_k > 8 || !a->tok || !a->ctrl || !a->active || !a->seq_state)
+        return set_error("hvx_llm_decode_leave: bad argument block"), -1;
+    if (slot < 0 || slot >= a->n_seq || slot >= h->n_slots) return set_error("hvx_llm_decode_leave: slot %d outside the bound grid of %d", slot, a->n_seq), -1;
+    AdvanceArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.n_seq = a->n_seq; aa.head_k = a->head_k;
+    aa.tok = a->tok; aa.ctrl = a->ctrl; aa.active = a->active; aa.seq_state = a->seq_state;
+    return launch_decode_leave(aa, slot, (hipStream_t)stream);
+}
+
 int hvx_llm_use_graph(hvx_llm* h, int32_t enable) {
     if (!h) return set_error("hvx_llm_use_graph: null handle"), -1;
     h->use_graph = enable != 0;

@@ -391,6 +391,32 @@ int launch_decode_join(const AdvanceArgs& a, long long* cursor, int slot, int fi
     return hipGetLastError() == hipSuccess ? 0 : (set_error("decode_join launch failed"), -1);
 }
 
+// The caller retires slot i of a running decode grid (a cancelled request): the state decode_advance_kernel leaves a finished sequence in,
+// ordered on the stream between two steps.  pos / out_len / steps, the utterance so far, the repetition ring, the cursor and the slot's
+// sampling and head rows stay as they are; seq_state word 7 says "retired by the caller".
+__global__ void decode_leave_kernel(AdvanceArgs a, int i) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (i < 0 || i >= a.n_seq) return;
+    const int K = a.head_k;
+    int* st = a.seq_state + i * 8;
+    const int pos = st[0];
+    for (int j = 0; j < K; ++j) a.tok[i * K + j] = -1;
+    a.ctrl[0 * a.n_seq + i] = i;
+    a.ctrl[1 * a.n_seq + i] = pos;
+    a.ctrl[2 * a.n_seq + i] = 0;
+    a.ctrl[3 * a.n_seq + i] = pos;
+    a.ctrl[4 * a.n_seq + i] = -1;
+    a.active[i] = 0;
+    st[2] = 1;
+    st[7] = 1;
+}
+
+int launch_decode_leave(const AdvanceArgs& a, int slot, hipStream_t s) {
+    if (slot < 0 || slot >= a.n_seq) return set_error("decode_leave: slot %d outside [0,%d)", slot, a.n_seq), -1;
+    hipLaunchKernelGGL(decode_leave_kernel, dim3(1), dim3(64), 0, s, a, slot);
+    return hipGetLastError() == hipSuccess ? 0 : (set_error("decode_leave launch failed"), -1);
+}
+
 int launch_decode_advance(const AdvanceArgs& a, hipStream_t s) {
     if (a.n_seq <= 0) return 0;
     hipLaunchKernelGGL(decode_advance_kernel, dim3((a.n_seq + 63) / 64), dim3(64), 0, s, a);

@@ -44,6 +44,14 @@ def _fresh_seed():
     return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
 
 
+class Cancelled(Exception):
+    """a request retired by its caller (the `cancel` object of its request dict was set).  `.tokens`: the ids that had surfaced by then"""
+
+    def __init__(self, tokens=()):
+        super().__init__('cancelled')
+        self.tokens = list(tokens)
+
+
 class _Request:
     def __init__(self, prefix_tok, n_text, min_len, max_len, noise):
         self.prefix = prefix_tok          # encoded int list (speech ids >= 0, text ids as -2-id)
@@ -59,6 +67,8 @@ class _Request:
         self.sp_error = None              # what was wrong with the parameters the request came with
         self.heads = None                 # own inference_head_num (a mixed-heads grid), as the request gave it; None = the LM's
         self.k = None                     # heads the request decodes with, set when it joins a mixed-heads grid
+        self.cancel = None                # any object with is_set(): once set, the engine retires the request (Cancelled)
+        self.cancelled = False
 
     def set_sampling(self, sampling):
         """the request's own top_p / top_k / win_size / tau_r, in any form sampling_params accepts; a bad set is kept as the request's error"""
@@ -348,7 +358,11 @@ class HvxLLM:
         stream_tokens: yields (tag, new ids, False) for every request whenever a host round trip (`sync_every` decode steps, default 8) surfaced ids of it,
         and (tag, token list | exception, True) when it is complete — the concatenated increments ARE that list, and the list is the one the switch off
         gives: the same launches, only more is read back.  Composes with mixed_sampling / mixed_heads.  A smaller `sync_every` gives a finer cadence
-        for more host round trips."""
+        for more host round trips.
+        cancel: a request dict may carry `cancel`, any object with is_set().  Once it is set the request is retired: one still waiting never takes a slot, one in
+        flight is taken off the grid on the device (hvx_llm_decode_leave, ordered on the decode stream) when the host next looks at a block's state, and its slot
+        goes to the next waiting request.  It comes back once as (tag, Cancelled) — with stream_tokens as (tag, Cancelled, True), the increments already yielded
+        stay valid and Cancelled.tokens is their concatenation.  The others decode what they decode without it."""
         n_slots = n_slots or self.max_batch
 
         def to_req(d):
@@ -362,6 +376,7 @@ class HvxLLM:
                 r.set_sampling(d['sampling'])
             if d.get('inference_head_num') is not None:
                 r.heads = int(d['inference_head_num'])
+            r.cancel = d.get('cancel')
             return r
         if hasattr(requests, 'poll'):
             # an open-ended polling source (the queue worker): poll(block) -> request dict | None, StopIteration when closed
@@ -699,7 +714,7 @@ class _DecodeEngine:
         emitted = 0
         launched = processed = 0
         draining = False                              # True while the queue is being emptied to re-allocate the noise ring
-        n_done = n_tokens = 0
+        n_done = n_tokens = n_cancelled = 0
         finished_clean = False
         t_setup = 0.0
         ready = []                                    # ('token', id) / ('done', request) waiting to be handed out
@@ -708,7 +723,10 @@ class _DecodeEngine:
             """next waiting request, if there is one.  `requests` is an iterator (next() may block: a finite job) or a polling source with
             poll(block) -> request | None ("nothing right now"; only asked to block while the grid is idle) that raises StopIteration when closed.
             A request that cannot run (context / output budget) is handed back at once with r.error set: the grid keeps running."""
-            nonlocal waiting, exhausted
+            nonlocal waiting, exhausted, n_cancelled
+            if waiting is not None and is_cancelled(waiting):     # cancelled while it waited for a slot: it never takes one
+                r, waiting = waiting, None
+                retire_waiting(r)
             while waiting is None and not exhausted:
                 try:
                     # (never block while something is waiting to be handed out: a refused request, a finished one — the source may stay silent for ever)
@@ -724,6 +742,36 @@ class _DecodeEngine:
                     r.out, r.done, r.error = [], True, err
                     r.noise.finalize(0)
                     ready.append(('done', r))
+                elif is_cancelled(waiting):                   # arrived already cancelled
+                    r, waiting = waiting, None
+                    retire_waiting(r)
+
+        def is_cancelled(r):
+            c = getattr(r, 'cancel', None)
+            return c is not None and c.is_set()
+
+        def retire_waiting(r):
+            nonlocal n_cancelled
+            r.out, r.done, r.cancelled, r.error = [], True, True, Cancelled([])
+            r.noise.finalize(0)
+            n_cancelled += 1
+            ready.append(('done', r))
+
+        def arrived(out_pin, r):
+            """the ids of a finished (or retired) request are on the host: hand it out"""
+            nonlocal n_done, n_tokens, n_cancelled
+            r.out = out_pin[:r.state[1]].tolist()
+            # (a retired request: the cursor of the snapshot at which the cancel was noticed.  The blocks already enqueued ahead of the leave went on consuming
+            # noise for the slot on the device; nobody reads those values' ids, so for a seeded request this is exact and for one without a seed the global
+            # generator is simply left a little earlier — accepted)
+            r.noise.finalize(r.cursor)
+            if r.cancelled:
+                r.error = Cancelled(r.out)
+                n_cancelled += 1
+            else:
+                n_done += 1
+                n_tokens += len(r.out)
+            ready.append(('done', r))
 
         def launch(slot):
             with torch.cuda.stream(stream):
@@ -831,11 +879,7 @@ class _DecodeEngine:
                     while pending_out:
                         ev, out_pin, r = pending_out.pop(0)
                         ev.synchronize()
-                        r.out = out_pin[:r.state[1]].tolist()
-                        r.noise.finalize(r.cursor)
-                        n_done += 1
-                        n_tokens += len(r.out)
-                        ready.append(('done', r))
+                        arrived(out_pin, r)
                     if ready:
                         continue
                     with torch.cuda.stream(stream):
@@ -901,6 +945,15 @@ class _DecodeEngine:
                             pending_out.append((ev, out_pin, r))
                             r.done = True
                             continue
+                        if is_cancelled(r):           # retired by its caller: the ids so far come back like a finished request's, the slot leaves the grid on the stream
+                            out_pin = torch.empty(max(st[i][1], 1), dtype=torch.int32).pin_memory()
+                            out_pin.copy_(self.out_dev[i, :max(st[i][1], 1)], non_blocking=True)
+                            ev = torch.cuda.Event()
+                            ev.record(stream)
+                            pending_out.append((ev, out_pin, r))
+                            check(llm.lib.hvx_llm_decode_leave(llm._h, C.c_void_p(stream.cuda_stream), C.byref(self.args), i), 'hvx_llm_decode_leave')
+                            r.done = r.cancelled = True
+                            continue
                         stall[i] = st[i][6] == 2      # waiting for noise: that sequence's steps are void until its ring is topped up
                     if self.stream_first and self.slot_req[0] is not None and blk >= self.join_block[0]:
                         n0 = self.slot_req[0].state[1]
@@ -928,21 +981,13 @@ class _DecodeEngine:
                 # requests whose ids have arrived
                 while pending_out and pending_out[0][0].query():
                     ev, out_pin, r = pending_out.pop(0)
-                    r.out = out_pin[:r.state[1]].tolist()
-                    r.noise.finalize(r.cursor)
-                    n_done += 1
-                    n_tokens += len(r.out)
-                    ready.append(('done', r))
+                    arrived(out_pin, r)
                 if len(self._keep) > 64:
                     self._keep = self._keep[-32:]     # their copies were enqueued before blocks that have completed since
             stream.synchronize()                      # a surplus block of inactive steps may still be running: it changes nothing
             while pending_out:
                 ev, out_pin, r = pending_out.pop(0)
-                r.out = out_pin[:r.state[1]].tolist()
-                r.noise.finalize(r.cursor)
-                n_done += 1
-                n_tokens += len(r.out)
-                ready.append(('done', r))
+                arrived(out_pin, r)
             finished_clean = True
             while ready:
                 yield ready.pop(0)
@@ -964,7 +1009,7 @@ class _DecodeEngine:
             seqs = sum(n for _, n, _ in timed) / n_blk if n_blk else 0.0
             ctx_sum = sum(p for _, _, p in timed) / n_blk if n_blk else 0.0
             self.stats = dict(steps=n_blk * sync_every, tokens=n_tokens, seconds=dt, tps=n_tokens / dt if dt > 0 else 0.0, head_k=K, batch=S,
-                              requests=n_done, prefill_and_setup_seconds=t_setup,
+                              requests=n_done, cancelled=n_cancelled, prefill_and_setup_seconds=t_setup,
                               device_idle_ms_between_blocks=sum(gaps), idle_gaps_over_1ms=[(i, round(g, 1)) for i, g in enumerate(gaps) if g > 1.0][:24], decode_step_us=1e3 * step_ms, decode_steps_timed=n_blk * sync_every,
                               mean_active_sequences=seqs, mean_ctx=ctx_sum / seqs if seqs else 0.0,
                               decode_step_bytes=llm.decode_step_bytes(1, K, ctx_sum), clean=finished_clean, mixed_sampling=self.mixed, mixed_heads=self.mixed_heads)

@@ -289,6 +289,11 @@ def merge_short_segments(segments, min_length=5):
     return out
 
 
+def segments_of(text):
+    """the pieces text_to_speech cuts a long text into (:782-800): at most 30 characters, at least 10"""
+    return merge_short_segments(split_text_by_punctuation(text, 30, 10), 10)
+
+
 def inference_tts_with_segmentation(model_manager, text, spk_id, max_length=30, min_length=10, last_prompt=True, speed=1.0):
     """(:357-452) piece-wise synthesis of a long text: the first piece (every piece when `last_prompt` is False) is plain speaker TTS,
     each later piece is zero-shot with the previous piece's text and audio as its prompt; pieces are joined with 50-150 ms of silence
@@ -345,7 +350,7 @@ def text_to_speech(model_manager, text, speaker_id, speed=1.0):
         segments_info = None
         if len(text) > SEGMENTED_TEXT_CHARS:
             audio = inference_tts_with_segmentation(model_manager, text, speaker_id, max_length=30, min_length=10, last_prompt=False, speed=speed)
-            segs = merge_short_segments(split_text_by_punctuation(text, 30, 10), 10)
+            segs = segments_of(text)
             segments_info = {'total_segments': len(segs), 'segments': segs}
         else:
             audio = inference_tts(model_manager, text, speaker_id, speed=speed)

@@ -15,7 +15,7 @@ import torch
 from .config import HvxConfig
 from .flow import HvxFlow
 from .hift import HvxHift
-from .llm import HvxLLM
+from .llm import Cancelled, HvxLLM
 from . import weights as W
 
 
@@ -34,6 +34,12 @@ class Utterance:
     min_token_text_ratio: Optional[float] = None
     sampling: object = None                                 # own top_p / top_k / win_size / tau_r (dict or partial) in a mixed-sampling grid; None: the LM's
     inference_head_num: Optional[int] = None                # own head count in a mixed-heads grid; None: the LM's
+    cancel: object = None                                   # any object with is_set() (serve): once set, the utterance is retired and comes back as Cancelled
+
+
+def _cancelled(u):
+    c = getattr(u, 'cancel', None)
+    return c is not None and c.is_set()
 
 
 @dataclass
@@ -111,6 +117,7 @@ class _StreamUtterance:
         self.pieces = 0
         self.tokens = None               # the utterance's full token list, once the LM has finished it
         self.t_fetch = t_fetch
+        self.dead = False                # cancelled by its caller: nothing more of it is solved; it leaves when the LM hands it back
 
     def flow_inputs(self, flow, n, final):
         """mu, spk, cond of the flow over the prompt and the first n generated tokens (HvxFlow.inference's plumbing)"""
@@ -368,7 +375,11 @@ class HvxPipeline:
         `abandoned`).  `event_log`: a list (or anything with append) that receives the engine's log as it happens — ('tokens', n, count) / ('done', n)
         from the LM thread, ('piece', n, index, final) from this one; nothing is logged without it (a server's serve() call may live for days).
         `sync_every`: decode steps per host round trip of the grid (default 8); smaller: tokens — and so pieces — surface at a finer cadence, for more
-        round trips."""
+        round trips.
+        Cancelling ONE utterance: `Utterance.cancel` (any object with is_set()) goes to the decode engine with the request (HvxLLM.generate_stream).  Unstreamed, a
+        cancelled utterance comes back once as (utterance, Cancelled, ids so far) — also when it is cancelled between its last token and its solve.  Streamed, its
+        chunk jobs not yet solved are dropped, its mel cache and state are released and it comes back once as (utterance, Cancelled, {}); pieces already handed
+        out are not recalled.  `self.last_continuous['cancelled']` counts them (the key is there when some utterance of the run carried `cancel`); they are not `abandoned`."""
         acoustic_batch = acoustic_batch or self.acoustic_batch
         acoustic_min_batch = max(1, min(int(acoustic_min_batch), acoustic_batch))
         piecewise = bool(stream)                           # (`stream` names the acoustic stage's device stream below)
@@ -417,7 +428,7 @@ class HvxPipeline:
         from collections import deque
         fetched = {}                                       # stream: running id -> (time of its fetch, tokens its mel cache must hold), until its session exists
         live = {}                                          # stream: running id -> _StreamUtterance, until its final piece has left
-        acct = dict(pieces=0, chunk_solves=0, first=deque(maxlen=4096), acoustic=0.0, audio=0.0, tokens=0)
+        acct = dict(pieces=0, chunk_solves=0, first=deque(maxlen=4096), acoustic=0.0, audio=0.0, tokens=0, cancelled=0, with_cancel=False)
 
         class _Requests:
             @staticmethod
@@ -439,6 +450,8 @@ class HvxPipeline:
                         raise StopIteration
                     tag = n_seen[0]
                     n_seen[0] += 1
+                    if getattr(u, 'cancel', None) is not None:
+                        acct['with_cancel'] = True
                     seen[tag] = u
                     if piecewise and u.speed != 1.0:          # (cosyvoice/cli/model.py:425) answered at once, it never takes a slot
                         if not put((tag, AssertionError('speed change only support non-stream inference mode'), True)):
@@ -449,7 +462,7 @@ class HvxPipeline:
                     budget = max_out if max_out is not None else int(len(u.text) * (max_token_text_ratio if u.max_token_text_ratio is None else u.max_token_text_ratio))
                     fetched[tag] = (time.time(), max(int(budget), 1))
                 return dict(text=u.text, prompt_text=u.prompt_text, prompt_speech_token=u.prompt_speech_token, seed=u.seed, tag=tag, sampling=u.sampling,
-                            inference_head_num=u.inference_head_num,
+                            inference_head_num=u.inference_head_num, **(dict(cancel=u.cancel) if getattr(u, 'cancel', None) is not None else {}),
                             max_token_text_ratio=max_token_text_ratio if u.max_token_text_ratio is None else u.max_token_text_ratio,
                             min_token_text_ratio=min_token_text_ratio if u.min_token_text_ratio is None else u.min_token_text_ratio)
 
@@ -510,9 +523,15 @@ class HvxPipeline:
                         tail, ended = nxt, True                    # (the sentinel / error is handled after this batch)
                         break
                     group.append(nxt)
+                # (cancelled between its last token and its solve: it never reaches the acoustic stage)
+                group = [(i, Cancelled(t) if not isinstance(t, BaseException) and _cancelled(seen[i]) else t) for i, t in group]
                 bad = [(i, t) for i, t in group if isinstance(t, BaseException) or not t]
                 group = [(i, t) for i, t in group if not isinstance(t, BaseException) and t]
                 for i, t in bad:
+                    if isinstance(t, Cancelled):
+                        acct['cancelled'] += 1
+                        yield seen.pop(i), t, list(t.tokens)
+                        continue
                     yield seen.pop(i), (t if isinstance(t, BaseException) else torch.zeros(0, device=self.device)), []
                 if group:
                     us = [seen[i] for i, _ in group]
@@ -540,6 +559,8 @@ class HvxPipeline:
             self.last_continuous = dict(tokens=tokens, audio_seconds=audio, acoustic_seconds=acoustic, total_seconds=time.time() - t_begin,
                                         llm_seconds=lm_info.get('seconds', 0.0), llm=lm_info.get('stats', {}), lm_slots=lm_slots,
                                         abandoned=abandoned + list(seen.values()))
+            if acct['with_cancel']:                                # (a run in which no utterance carried `cancel` reports what it always reported)
+                self.last_continuous['cancelled'] = acct['cancelled']
             if piecewise:
                 self.last_continuous.update(tokens=acct['tokens'], audio_seconds=acct['audio'], acoustic_seconds=acct['acoustic'], pieces=acct['pieces'],
                                             chunk_solves=acct['chunk_solves'], first_piece_seconds=list(acct['first']),
@@ -583,13 +604,19 @@ class HvxPipeline:
                 if isinstance(item, BaseException):
                     raise item
                 n, ids, done = item
-                if not done:
+                if n in live and live[n].dead:                     # retired here already: the LM's last word on it is all that is waited for
+                    if done:
+                        drop(n)
+                        acct['cancelled'] += 1
+                        yield seen.pop(n), ids if isinstance(ids, Cancelled) else Cancelled(ids if not isinstance(ids, BaseException) else ()), {}
+                elif not done:
                     se = session(n)
                     for k, covered in se.sched.feed(ids):
                         se.jobs.append((k, covered, False))
                         order.append(n)
                 elif isinstance(ids, BaseException):
                     drop(n)
+                    acct['cancelled'] += isinstance(ids, Cancelled)
                     yield seen.pop(n), ids, {}
                 elif not ids:                                      # nothing was generated: one empty, final piece
                     drop(n)
@@ -605,6 +632,16 @@ class HvxPipeline:
                     se.tokens = list(ids)
                     se.jobs.append((k, covered, True))
                     order.append(n)
+            # ---- utterances cancelled by their caller: their jobs go; one the LM has finished leaves here, the others when the LM hands them back
+            for n, se in list(live.items()):
+                if se.dead or not _cancelled(se.u):
+                    continue
+                se.dead, se.jobs = True, []
+                order[:] = [m for m in order if m != n]
+                if se.tokens is not None:
+                    drop(n)
+                    acct['cancelled'] += 1
+                    yield seen.pop(n), Cancelled(se.tokens), {}
             if not order:
                 if ended:
                     return

@@ -338,6 +338,14 @@ int hvx_llm_decode_join_seq(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, 
 int hvx_llm_decode_join_mixed(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, const hvx_seq_sampling* q, const hvx_seq_heads* heads,
                               int32_t slot, int32_t first_tok, int32_t pos, int32_t min_len, int32_t max_len, int32_t top_k, float top_p,
                               int32_t win_size, int32_t rep_thresh, int32_t head_k);
+/* The caller retires slot `slot` of the running grid described by `a` (a cancelled request), between two hvx_llm_decode_steps* calls on the
+ * same stream: one small kernel puts the slot into the state `advance` leaves a finished sequence in — its tok rows -1,
+ * ctrl = {slot, pos, 0, pos, -1}, active 0, seq_state done = 1 — and sets the so-far reserved word 7 of its seq_state row to 1 ("retired by
+ * the caller").  pos, out_len, steps, out_tokens, the repetition ring, the cursor and the slot's sampling / head entries are untouched: the
+ * ids decoded so far can still be read.  Steps replayed after it treat the slot like any finished one (with hvx_llm_decode_steps_mixed,
+ * heads_live need not cover it any more), and a later hvx_llm_decode_join* of the slot works as before.  Refused — -1, hvx_last_error,
+ * nothing launched — for a slot outside [0, a->n_seq) and a null or invalid argument block. */
+int hvx_llm_decode_leave(hvx_llm* h, hvx_stream s, const hvx_decode_args* a, int32_t slot);
 /* debugging / parity: copy the post-final-norm hidden of the last rows of the previous forward (fp32 [n_seq][H]) */
 int hvx_llm_last_hidden(hvx_llm* h, hvx_stream s, int32_t n_seq, float* out);
 

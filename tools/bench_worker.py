@@ -4,6 +4,7 @@ bench workload: N `tts` tasks of 512 text tokens pushed through a queue, HydraVo
 weights; a stand-in frontend turns the task text into token ids (the real text / audio frontends are outside this build).
 
     python tools/bench_worker.py [--tasks 64] [--chars 512] [--lm-slots 64] [--acoustic-batch 4] [--one-by-one] [--alternate-sampling] [--mixed-sampling] [--alternate-heads] [--mixed-heads]
+    python tools/bench_worker.py --long-text [--lm-slots 64] [--acoustic-batch 4]
 
 --alternate-sampling: the tasks carry `extra_params` that alternate between two sampling parameter sets (same inference_head_num) — the worst
 case for the worker's epochs: without --mixed-sampling every task closes the running decode grid.  --mixed-sampling serves the queue with
@@ -11,6 +12,10 @@ serve_queue(mixed_sampling=True): the parameters are per-sequence state of the g
 --alternate-heads: the tasks carry `extra_params` that alternate between two head counts (2 and 5, same sampling parameters); without
 --mixed-heads every task closes the running grid, with it (serve_queue(mixed_heads=True)) they share one grid of head_num rows per sequence.
 The A/B is four runs — off, on, off, on — each in its own process on the same box.
+--long-text: another workload, both settings in THIS process: one `tts` task of 5001+ characters followed by eight 64-character tasks (text ids by
+character, 5.5 speech tokens per character), served by serve_queue with segment_fanout off (the long task drains the grid and runs segment by
+segment between two epochs) and on (its ~170 segments share the grid with everybody), same task seeds.  Prints, per setting, the seconds until the
+long task's result, until the last short task's result, and epochs / epoch_boundaries.
 """
 import argparse
 import json
@@ -35,7 +40,10 @@ ap.add_argument('--alternate-sampling', action='store_true', help='tasks alterna
 ap.add_argument('--mixed-sampling', action='store_true', help='serve_queue(mixed_sampling=True): requests with different sampling parameters share the grid')
 ap.add_argument('--alternate-heads', action='store_true', help='tasks alternate between two head counts (extra_params.inference_head_num = 2 / 5)')
 ap.add_argument('--mixed-heads', action='store_true', help='serve_queue(mixed_heads=True): requests with different head counts share the grid')
+ap.add_argument('--long-text', action='store_true', help='one 5001+ character task and eight 64-character tasks, serve_queue(segment_fanout) off and on')
 a = ap.parse_args()
+if a.long_text:
+    a.chars = 96                                         # sizes the models for the longest utterance of that workload: 64 characters, and the unsegmented warm-up text (under 70)
 from flowmirror_hydravox_amd import cv3_config, weights as W  # noqa: E402
 from flowmirror_hydravox_amd.flow import HvxFlow  # noqa: E402
 from flowmirror_hydravox_amd.hift import HvxHift  # noqa: E402
@@ -54,6 +62,10 @@ class Frontend:
         return [text] if split else text
 
     def frontend_sft(self, text, spk_id):
+        if a.long_text:                                  # real texts: one id per character
+            g = torch.Generator().manual_seed(len(text))
+            return dict(text=torch.tensor([[(ord(c) * 7919) % 151643 for c in text]], dtype=torch.int32), text_len=torch.tensor([len(text)], dtype=torch.int32),
+                        llm_embedding=torch.zeros(0, 192), flow_embedding=torch.randn(192, generator=g))
         g = torch.Generator().manual_seed(int(text))
         return dict(text=torch.randint(0, 151643, (1, a.chars), generator=g, dtype=torch.int32), text_len=torch.tensor([a.chars], dtype=torch.int32),
                     llm_embedding=torch.zeros(0, 192), flow_embedding=torch.randn(192, generator=g))
@@ -112,6 +124,50 @@ def run(n, one_by_one):
     return dt, audio
 
 
+class _Timed(dict):
+    """a result dict that notes when every key was written"""
+
+    def __init__(self, t0):
+        super().__init__()
+        self.t0, self.at = t0, {}
+
+    def __setitem__(self, k, v):
+        self.at.setdefault(k, time.time() - self.t0)
+        super().__setitem__(k, v)
+
+
+def long_text(n_chars, n_short, fanout, chars=None):
+    words = ['lorem', 'ipsum', 'dolor', 'sit', 'amet', 'consectetur', 'adipiscing', 'elit', 'sed', 'do']
+    text, k = '', 0
+    while len(text) < n_chars:                           # a sentence mark every three words: pieces of 15 .. 30 characters
+        text += ' '.join(words[(k + j) % len(words)] for j in range(3)) + '.,;!?'[k % 5] + ' '
+        k += 1
+    q = queue.Queue()
+    q.put(dict(id='long', task_type='tts', text=text, speaker_id='s', seed=1000))
+    for i in range(n_short):
+        q.put(dict(id='short%d' % i, task_type='tts', text=('short task number %d ' % i + 'x' * 64)[:64], speaker_id='s', seed=2000 + i))
+    q.put(None)
+    orig = llm.inference                                 # (the one-by-one path of the switch-off run calls llm.inference with the default ratios)
+    llm.inference = lambda **kw: orig(**dict(kw, max_token_text_ratio=ratio, min_token_text_ratio=ratio))
+    torch.cuda.synchronize()
+    results = _Timed(time.time())
+    try:
+        st = serve_queue(mm, q, results, lm_slots=a.lm_slots, acoustic_batch=a.acoustic_batch, normalise=lambda s: s, segment_fanout=fanout, segmented_text_chars=chars)
+    finally:
+        llm.inference = orig
+    torch.cuda.synchronize()
+    assert all('output_audio' in results[k] for k in ['long'] + ['short%d' % i for i in range(n_short)]), [r for r in results.values() if 'error' in r][:2]
+    return dict(segment_fanout=fanout, chars=len(text), segments=(results['long']['segments_info'] or {}).get('total_segments'), long_task_seconds=round(results.at['long'], 3),
+                last_short_task_seconds=round(max(results.at['short%d' % i] for i in range(n_short)), 3), audio_seconds=round(sum(r['duration'] for r in results.values()), 2),
+                epochs=st['epochs'], epoch_boundaries=st['epoch_boundaries'], fanned_out=st['fanned_out'])
+
+
+if a.long_text:
+    for fanout in (False, True):                         # warm-up of both paths (graphs, workspaces) on a small job of the same kind
+        long_text(40, 2, fanout, chars=30)               # (40 .. 68 characters: off, one plain utterance on the one-by-one path; on, two or three segments)
+    runs = [long_text(5001, 8, fanout) for fanout in (False, True)]
+    print(json.dumps({'path': 'worker.serve_queue, one long tts task + 8 short ones', 'lm_slots': a.lm_slots, 'acoustic_batch': a.acoustic_batch, 'off': runs[0], 'on': runs[1]}))
+    sys.exit(0)
 run(min(a.tasks, 4), a.one_by_one)                       # warm-up (graphs, workspaces)
 dt, audio = run(a.tasks, a.one_by_one)
 print(json.dumps({'path': 'worker_process_tts (one task at a time, reference loop)' if a.one_by_one else 'worker.serve_queue (continuous engine)', 'tasks': a.tasks,
