@@ -11,6 +11,9 @@ LIB_EXPLICIT = bool(os.environ.get('HVX_LIB_PATH'))
 
 F32, BF16, F16 = 0, 1, 2
 
+# Epi codes (csrc/hvx_kernels.h): hvx_gemm_args.epi
+EPI_GENERIC, EPI_QKV_DIT = 0, 1
+
 # Act codes (csrc/hvx_device.h)
 ACT_NONE, ACT_GELU_TANH, ACT_SILU, ACT_MISH, ACT_ELU, ACT_LRELU, ACT_SNAKE, ACT_TANH, ACT_ABS = range(9)
 
@@ -56,7 +59,9 @@ class GemmArgs(C.Structure):
                 ('ldo2', c_i32), ('out2_row_off', c_i32), ('out2_cols', c_i32), ('x3', c_i32), ('res_f16', c_i32), ('out_f16', c_i32),
                 ('a_planes', c_i32), ('a_plane', c_i64), ('w_planes', c_i32), ('w_plane', c_i64),
                 ('out_planes', c_i32), ('out_plane', c_i64), ('out2_planes', c_i32), ('out2_plane', c_i64),
-                ('res2', c_vp), ('res2_bs', c_i64), ('ldres2', c_i32), ('div', c_f32)]
+                ('res2', c_vp), ('res2_bs', c_i64), ('ldres2', c_i32), ('div', c_f32),
+                ('epi', c_i32), ('q', c_vp), ('k', c_vp), ('vT', c_vp), ('heads', c_i32), ('t_pad', c_i32),
+                ('rope_cos', c_vp), ('rope_sin', c_vp), ('q_scale', c_f32), ('qkv_f16', c_i32)]
 
 
 class AttnArgs(C.Structure):
@@ -261,7 +266,8 @@ SYMBOLS = {
 # hvx_llm_decode_join_seq and their hvx_seq_sampling block) joined the same way: additive, no existing struct or symbol touched; so did the
 # per-sequence head counts (hvx_ras_sample_mixed, hvx_llm_decode_steps_mixed, hvx_llm_decode_join_mixed and hvx_seq_heads), and the streaming batch of the
 # serving engine (hvx_cfm_solve_stream_batch, hvx_op_mel_cache_append), and hvx_llm_decode_leave (a cancelled request's slot is retired on the stream).
-HVX_ABI_VERSION = 7
+# 8: the epi / q / k / vT / heads / t_pad / rope_* / q_scale / qkv_f16 fields of hvx_gemm_args, for the parity tests of the fused QKV epilogue (ops.qkv_gemm).
+HVX_ABI_VERSION = 8
 
 _lib = None
 

@@ -251,6 +251,9 @@ int launch_form(const GemmArgs& a, hipStream_t s, long long min_tiles) {
     // Column groups of 4 tiles: the W panels of a group (4 x 256 rows x K bf16 = 2-4 MiB at K = 1024-2048) fit the XCD's L2; with all 8-12 column
     // tiles in one sweep W (4-6 MiB) is re-fetched through the fabric for every row tile (FETCH_SIZE 530 MB per QKV launch for 98 MB of operands).
     // Measured at M = 45056: N = 3072 330 -> 302 us, N = 2048 214 -> 204 us; N = 1024 has four column tiles anyway.
+    // the lean QKV pass loads the bias and the RoPE rows as f32x4
+    if (a.epi == EPI_QKV_DIT && ((((unsigned long long)a.bias) | ((unsigned long long)a.rope_cos) | ((unsigned long long)a.rope_sin)) & 15))
+        return set_error("gemm (256-tile form): the QKV bias and RoPE tables must be 16-byte aligned"), -1;
     const int gw_env = (int)opt(OPT_GEMM_BIG_GW);     // (tuning option; 0 = all columns in one group)
     int gw = tiles_n;
     if (gw_env > 0 && gw_env < tiles_n && tiles_n % gw_env == 0) gw = gw_env;

@@ -262,9 +262,18 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
         set_error("launch_gemm: bad geometry M=%d N=%d K=%d cin_pad=%d lda=%d up=%d", a.M, a.N, a.K, a.cin_pad, a.lda, a.up);
         return -1;
     }
-    if (a.epi == EPI_QKV_DIT && (a.N != 3 * a.heads * 64 || (a.t_pad & 3) || a.groups != 1)) {
-        set_error("launch_gemm: bad QKV geometry N=%d heads=%d t_pad=%d", a.N, a.heads, a.t_pad);
-        return -1;
+    if (a.epi == EPI_QKV_DIT) {
+        // what the QKV epilogue (gemm_epilogue.h) assumes and does not check: rows t < M of q / k and columns t < M of V^T are addressed with the pitch t_pad, and every
+        // form writes them with 16-byte stores (store8)
+        if (a.N != 3 * a.heads * 64 || (a.t_pad & 3) || a.groups != 1) return set_error("launch_gemm: bad QKV geometry N=%d heads=%d t_pad=%d", a.N, a.heads, a.t_pad), -1;
+        if (a.t_pad < a.M) return set_error("launch_gemm: QKV t_pad=%d is shorter than M=%d", a.t_pad, a.M), -1;
+        const int qes = a.dtype == DT_F32 ? 4 : 2;
+        if (((long long)a.t_pad * qes) & 15) return set_error("launch_gemm: QKV t_pad=%d: the rows of V^T must be a multiple of 16 bytes (%d elements)", a.t_pad, 16 / qes), -1;
+        if (!a.q || !a.k || !a.vT) return set_error("launch_gemm: QKV epilogue with a null q, k or vT"), -1;
+        if ((((unsigned long long)a.q) | ((unsigned long long)a.k) | ((unsigned long long)a.vT)) & 15) return set_error("launch_gemm: QKV q, k and vT must be 16-byte aligned"), -1;
+        if (!a.rope_cos != !a.rope_sin) return set_error("launch_gemm: QKV epilogue with one RoPE table and not the other"), -1;
+        if (a.qkv_f16 && a.dtype != DT_F16) return set_error("launch_gemm: qkv_f16 needs fp16 operands (dtype %d)", a.dtype), -1;
+        if (a.x3 || a.a_planes || a.w_planes) return set_error("launch_gemm: the QKV epilogue exists for plain operands only (x3=%d a_planes=%d w_planes=%d)", a.x3, a.a_planes, a.w_planes), -1;
     }
     const int x3 = launch_gemm_x3(a, s);                   // fp32 operands split into bf16 pairs (gemm_x3.hip), where the caller allows it
     if (x3) return x3 < 0 ? -1 : 0;

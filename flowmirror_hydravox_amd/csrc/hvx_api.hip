@@ -240,7 +240,11 @@ int hvx_op_gemm(const hvx_gemm_args* a, hvx_stream s) {
     g.dtype = a->dtype; g.M = a->M; g.N = a->N; g.K = a->K; g.batch = a->batch; g.groups = a->groups;
     g.A = a->A; g.a_bs = a->a_bs; g.lda = a->lda; g.a_gs = a->a_gs; g.rows_in = a->rows_in;
     g.cin_pad = a->cin_pad; g.conv_stride = a->conv_stride; g.conv_dil = a->conv_dil; g.pad_left = a->pad_left; g.up = a->up;
-    g.W = a->W; g.w_gs = a->w_gs; g.epi = EPI_GENERIC;
+    g.W = a->W; g.w_gs = a->w_gs;
+    if (a->epi != EPI_GENERIC && a->epi != EPI_QKV_DIT) return set_error("hvx_op_gemm: epi %d: 0 (generic) or 1 (fused QKV)", a->epi), -1;
+    g.epi = a->epi;
+    g.q = a->q; g.k = a->k; g.vT = a->vT; g.heads = a->heads; g.t_pad = a->t_pad; g.rope_cos = a->rope_cos; g.rope_sin = a->rope_sin;
+    g.q_scale = a->q_scale; g.qkv_f16 = a->qkv_f16;
     g.bias = a->bias; g.act = a->act; g.act_param = a->act_param; g.act_alpha = a->act_alpha;
     g.gate = a->gate; g.gate_bs = a->gate_bs;
     g.res = a->res; g.res_bs = a->res_bs; g.ldres = a->ldres; g.res_row_off = a->res_row_off;

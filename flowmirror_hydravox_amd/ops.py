@@ -80,6 +80,46 @@ def conv1d(x, w_packed, bias, *, n_out, taps, cin_pad, pad_left=0, dil=1, stride
     return out
 
 
+def qkv_gemm_args(x, w, bias, *, heads, t_pad, rope=None, q_scale=0.0, qkv_dtype=None, q=None, k=None, vT=None):
+    """the hvx_gemm_args of ops.qkv_gemm and the (q, k, vT) buffers they point to, nothing launched (a test alters a field and calls hvx_op_gemm itself)"""
+    B, M, K = x.shape
+    N = 3 * heads * 64
+    assert x.stride(2) == 1 and w.dtype == x.dtype and tuple(w.shape) == (N, K) and w.is_contiguous(), (x.stride(), w.dtype, w.shape)
+    assert bias is None or (bias.dtype == torch.float32 and bias.numel() == N)
+    if qkv_dtype is None:
+        qkv_dtype = torch.float32 if x.dtype == torch.float32 else torch.bfloat16
+    bufs = []
+    for t, shape in ((q, (B, heads, t_pad, 64)), (k, (B, heads, t_pad, 64)), (vT, (B, heads, 64, t_pad))):
+        if t is None:
+            t = torch.zeros(shape, dtype=qkv_dtype, device=x.device)
+        assert t.dtype == qkv_dtype, (t.dtype, qkv_dtype)
+        bufs.append(t)
+    a = GemmArgs()
+    a.dtype, a.M, a.N, a.K, a.batch, a.groups = dtype_code(x.dtype), M, N, K, B, 1
+    (a.a_bs, a.lda), a.A, a.rows_in = _strides(x), ptr(x), M
+    a.cin_pad, a.conv_stride, a.conv_dil, a.pad_left, a.up = K, 1, 1, 0, 1
+    a.W, a.w_gs, a.bias, a.scale = ptr(w), N * K, ptr(bias), 1.0
+    a.epi, a.heads, a.t_pad, a.q_scale = _lib.EPI_QKV_DIT, heads, t_pad, q_scale
+    a.q, a.k, a.vT = (ptr(t) for t in bufs)
+    if rope is not None:
+        for t in rope:
+            assert t is None or (t.dtype == torch.float32 and tuple(t.shape) == (M, 32) and t.stride(1) == 1 and t.stride(0) == 32), (t.dtype, t.shape, t.stride())
+        a.rope_cos, a.rope_sin = ptr(rope[0]), ptr(rope[1])
+    a.qkv_f16 = int(qkv_dtype == torch.float16)
+    return a, tuple(bufs)
+
+
+def qkv_gemm(x, w, bias, *, heads, t_pad, rope=None, q_scale=0.0, qkv_dtype=None, q=None, k=None, vT=None):
+    """The fused QKV Linear of the DiT / Matcha transformer blocks, one launch (csrc/gemm_epilogue.h: EPI_QKV_DIT).  x: [B][M][K] (f32, bf16 or f16),
+    w: [3 * heads * 64][K] in the same dtype, bias: f32 [3 * heads * 64] or None, rope: (cos, sin), f32 [M][32] each, or None; q_scale 0.0: q is not scaled.
+    -> (q, k, vT): q, k [B][heads][t_pad][64], vT [B][heads][64][t_pad], in qkv_dtype — bf16 for bf16 and for f16 operands, f32 for f32 operands, torch.float16
+    (f16 operands only) selects the kernel that writes IEEE fp16.  Caller-provided buffers are written in place (rows / columns t < M only); absent ones are
+    allocated zero-filled.  What the kernels cannot take (include/hvx.h: hvx_gemm_args.epi) raises HvxError before anything is launched."""
+    a, bufs = qkv_gemm_args(x, w, bias, heads=heads, t_pad=t_pad, rope=rope, q_scale=q_scale, qkv_dtype=qkv_dtype, q=q, k=k, vT=vT)
+    check(_lib.load().hvx_op_gemm(C.byref(a), stream_ptr()), 'hvx_op_gemm')
+    return bufs
+
+
 def act_rows(x, act, *, act_param=0.0, alpha=None, out=None, plane=None):
     """y = act(x) for an fp32 [rows][ldx] matrix (per-column alpha for Snake).  plane None: fp32 `out` (allocated when absent); else `out` is a bf16
     buffer [rows][ldy] at the hi plane of a (hi, lo) pair whose lo plane lies `plane` elements behind (elementwise.hip: act_rows_planes_kernel)."""

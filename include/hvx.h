@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define HVX_ABI_VERSION 7
+#define HVX_ABI_VERSION 8
 #define HVX_F32 0
 #define HVX_BF16 1
 #define HVX_F16 2                         /* IEEE fp16: hvx_flow_config.dtype only (the flow's fp16 mode) */
@@ -128,6 +128,18 @@ typedef struct {
     int32_t out2_planes; int64_t out2_plane;
     const float* res2; int64_t res2_bs; int32_t ldres2;   /* second fp32 residual, read at row m (no row offset) */
     float div;         /* != 0: the value is divided by it after `scale` (the mean over the ResBlocks of a vocoder stage) */
+    /* epi 0: the generic epilogue above.  epi 1: the fused QKV epilogue of the DiT / Matcha transformer blocks (csrc/hvx_kernels.h: EPI_QKV_DIT); act / gate / res /
+     * scale / out / out2 are not read.  N == 3 * heads * 64, groups == 1, a plain Linear (no x3, no plane pairs).  x = A W^T + bias; interleaved-pair RoPE on channels
+     * [0, 64) of q and of k (head 0 only: out[2i] = x[2i] c - x[2i+1] s, out[2i+1] = x[2i+1] c + x[2i] s, c / s = rope_cos / rope_sin[t][i], fp32 tables [M][32],
+     * both or neither); q *= q_scale where q_scale != 0; rows t < M land in q, k [batch][heads][t_pad][64] and vT [batch][heads][64][t_pad], nothing else of the three
+     * buffers is written.  They hold bf16 for bf16 AND for fp16 operands, fp32 for fp32 operands; qkv_f16 (fp16 operands only): IEEE fp16, saturated at +-65504.
+     * t_pad >= M; t_pad % 8 == 0 (fp32: % 4); q, k, vT 16-byte aligned (bias and the tables too where the 256-tile form takes the launch). */
+    int32_t epi;
+    void* q; void* k; void* vT;
+    int32_t heads, t_pad;
+    const float* rope_cos; const float* rope_sin;
+    float q_scale;
+    int32_t qkv_f16;
 } hvx_gemm_args;
 /* implicit-GEMM Conv1d / Linear on MFMA (torch.nn.functional.conv1d / linear call sites of the path) */
 int hvx_op_gemm(const hvx_gemm_args* a, hvx_stream s);

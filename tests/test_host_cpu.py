@@ -39,7 +39,7 @@ def test_library_builds_and_exports_every_declared_symbol():
         assert hasattr(lib, name), 'libhvx.so does not export %s' % name
     # the ctypes binding covers exactly the header
     assert sorted(_lib.SYMBOLS.keys()) == declared
-    assert _lib.load().hvx_abi_version() == _lib.HVX_ABI_VERSION == 7
+    assert _lib.load().hvx_abi_version() == _lib.HVX_ABI_VERSION == 8
 
 
 def test_libhvx_holds_no_packed_fp32_instruction(tmp_path):

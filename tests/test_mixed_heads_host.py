@@ -128,7 +128,7 @@ def test_header_declares_and_ctypes_binds_the_mixed_entry_points(tmp_path):
         assert re.search(r'\bint\s+%s\s*\(' % name, src), name
         assert name in _lib.SYMBOLS, name
     assert [len(_lib.SYMBOLS[n][1]) for n in ('hvx_ras_sample_mixed', 'hvx_llm_decode_steps_mixed', 'hvx_llm_decode_join_mixed')] == [4, 7, 15]
-    assert re.search(r'#define\s+HVX_ABI_VERSION\s+7\b', src)
+    assert re.search(r'#define\s+HVX_ABI_VERSION\s+8\b', src)
     c = tmp_path / 's.c'
     c.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hvx.h"\n'
                  'int main(){printf("%zu %zu\\n", sizeof(hvx_seq_heads), offsetof(hvx_seq_heads, head_k));return 0;}\n')
@@ -139,7 +139,7 @@ def test_header_declares_and_ctypes_binds_the_mixed_entry_points(tmp_path):
     lib = _lib.load()                                          # binds every symbol of SYMBOLS, the three new ones included, or raises
     for name in ('hvx_ras_sample_mixed', 'hvx_llm_decode_steps_mixed', 'hvx_llm_decode_join_mixed'):
         assert getattr(lib, name) is not None
-    assert lib.hvx_abi_version() == _lib.HVX_ABI_VERSION == 7
+    assert lib.hvx_abi_version() == _lib.HVX_ABI_VERSION == 8
     # refusals that need no device: a heads block without its array, null arguments
     a, hd = _lib.SampleArgs(), _lib.SeqHeads()
     assert lib.hvx_ras_sample_mixed(ctypes.byref(a), None, ctypes.byref(hd), None) == -1 and b'heads block' in lib.hvx_last_error()

@@ -101,7 +101,7 @@ def test_header_declares_and_ctypes_binds_the_seq_entry_points(tmp_path):
         assert re.search(r'\bint\s+%s\s*\(' % name, src), name
         assert name in _lib.SYMBOLS, name
     assert len(_lib.SYMBOLS['hvx_llm_decode_join_seq'][1]) == 13 and len(_lib.SYMBOLS['hvx_llm_decode_steps_seq'][1]) == 5
-    assert re.search(r'#define\s+HVX_ABI_VERSION\s+7\b', src)
+    assert re.search(r'#define\s+HVX_ABI_VERSION\s+8\b', src)
     c = tmp_path / 's.c'
     c.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hvx.h"\nint main(){printf("%zu %zu %zu %zu %zu\\n", sizeof(hvx_seq_sampling), '
                  'offsetof(hvx_seq_sampling, top_k), offsetof(hvx_seq_sampling, top_p), offsetof(hvx_seq_sampling, win_size), '
@@ -112,7 +112,7 @@ def test_header_declares_and_ctypes_binds_the_seq_entry_points(tmp_path):
     S = _lib.SeqSampling
     assert got == [ctypes.sizeof(S), S.top_k.offset, S.top_p.offset, S.win_size.offset, S.rep_thresh.offset]
     lib = _lib.load()                                          # binds every symbol of SYMBOLS, the three new ones included, or raises
-    assert lib.hvx_abi_version() == _lib.HVX_ABI_VERSION == 7
+    assert lib.hvx_abi_version() == _lib.HVX_ABI_VERSION == 8
     # refusals that need no device: a sampling block with a missing array, a join without a block
     a, q = _lib.SampleArgs(), _lib.SeqSampling()
     q.top_k = 16
