@@ -248,6 +248,20 @@ SYMBOLS = {
     'hvx_hift_source': (c_i32, [c_vp, c_vp, c_vp, c_sz, c_vp, c_i32, c_vp, c_vp]),
     'hvx_hift_decode': (c_i32, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_i32, c_vp]),
     'hvx_hift_decode_chunk': (c_i32, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    # the streaming vocoder (hift.HiftStream): additive at ABI 8
+    'hvx_hift_left_context': (c_i32, [c_vp, C.POINTER(c_i32), C.POINTER(c_i32)]),
+    'hvx_hift_stream_piece_samples': (c_i64, [c_vp, c_i32, c_i32, c_i32]),
+    'hvx_hift_stream_create': (c_i32, [c_vp, c_i32, C.POINTER(c_vp)]),
+    'hvx_hift_stream_destroy': (None, [c_vp]),
+    'hvx_hift_stream_reset': (c_i32, [c_vp]),
+    'hvx_hift_stream_state_bytes': (c_sz, [c_vp, c_i32]),
+    'hvx_hift_stream_bind': (c_i32, [c_vp, c_vp, c_sz, c_vp, c_i64]),
+    'hvx_hift_stream_set_context': (c_i32, [c_vp, c_i32, c_i32]),
+    'hvx_hift_stream_set_inputs': (c_i32, [c_vp, c_vp, c_vp]),
+    'hvx_hift_stream_workspace_bytes': (c_sz, [c_vp, c_i32]),
+    'hvx_hift_stream_plan': (c_i32, [c_vp, c_i32, c_i32, C.POINTER(c_i64)]),
+    'hvx_hift_stream_info': (c_i32, [c_vp, C.POINTER(c_i64)]),
+    'hvx_hift_stream_piece': (c_i32, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64]),
     'hvx_nd_elementwise': (c_i32, [c_i32, C.POINTER(NdDesc), c_vp, c_vp, c_vp, C.c_float, C.c_float, c_vp, c_vp]),
     'hvx_rows_reduce': (c_i32, [c_i32, c_vp, c_i64, c_i64, c_vp, c_vp]),
     'hvx_rows_softmax': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp]),
@@ -266,6 +280,7 @@ SYMBOLS = {
 # hvx_llm_decode_join_seq and their hvx_seq_sampling block) joined the same way: additive, no existing struct or symbol touched; so did the
 # per-sequence head counts (hvx_ras_sample_mixed, hvx_llm_decode_steps_mixed, hvx_llm_decode_join_mixed and hvx_seq_heads), and the streaming batch of the
 # serving engine (hvx_cfm_solve_stream_batch, hvx_op_mel_cache_append), and hvx_llm_decode_leave (a cancelled request's slot is retired on the stream).
+# The streaming vocoder (hvx_hift_left_context, hvx_hift_stream_*) joined at 8 the same additive way.
 # 8: the epi / q / k / vT / heads / t_pad / rope_* / q_scale / qkv_f16 fields of hvx_gemm_args, for the parity tests of the fused QKV epilogue (ops.qkv_gemm).
 HVX_ABI_VERSION = 8
 

@@ -72,6 +72,80 @@ int launch_hift_source(const float* f0, const float* phase, const float* table, 
     return hipGetLastError() == hipSuccess ? 0 : (set_error("hift_source launch failed"), -1);
 }
 
+// ---- the same two stages for the streaming vocoder (hvx_hift_stream_piece): absolute frames / samples, carried sums ----------------------
+// hift_phase_kernel over frames [t_a, t_b) only: the per-frame expression, the 256 runs and the double accumulation are that kernel's; the serial
+// prefix starts from the sum carried after frame t_a - 1 (0 at t_a == 0) instead of 0.  A scan continued piece by piece and a scan from frame 0
+// add the same doubles in another association, so they agree as that kernel's comment says: <= 1e-16 relative before the rounding to fp32.
+__global__ __launch_bounds__(256) void hift_phase_continue_kernel(const float* f0, float* phase, double* sums, long long* counters, int t_a,
+                                                                   int t_b, int H, float sr, float up, long long samples) {
+    __shared__ double part[256];
+    const int h = blockIdx.x, i = threadIdx.x;
+    const float mult = (float)(h + 1);
+    const int n = t_b - t_a;
+    const int per = (n + 255) / 256, t0 = min(t_b, t_a + i * per), t1 = min(t_b, t0 + per);
+    auto rad_of = [&](int t) {
+        float rad = (f0[t] * mult) / sr;
+        return rad - floorf(rad);
+    };
+    double sum = 0.0;
+    for (int t = t0; t < t1; ++t) sum += (double)rad_of(t);
+    part[i] = sum;
+    __syncthreads();
+    if (i == 0) {
+        double run = t_a > 0 ? sums[h] : 0.0;
+        for (int j = 0; j < 256; ++j) {
+            const double v = part[j];
+            part[j] = run;
+            run += v;
+        }
+    }
+    __syncthreads();
+    double cum = part[i];
+    for (int t = t0; t < t1; ++t) {
+        cum += (double)rad_of(t);
+        const float c = (float)cum;
+        phase[(long long)t * H + h] = ((c * 2.0f) * 3.14159274101257324f) * up;
+    }
+    if (t0 < t1 && t1 == t_b) {                  // the run that ends the piece carries its sum on: the next piece continues what produced row t_b - 1
+        sums[h] = cum;
+        if (h == 0) {
+            counters[0] = t_b;
+            counters[1] = samples;
+        }
+    }
+}
+int launch_hift_phase_continue(const float* f0, float* phase, double* sums, long long* counters, int t_a, int t_b, int H, float sr, int up,
+                               long long samples, hipStream_t s) {
+    if (t_b <= t_a) return 0;
+    hipLaunchKernelGGL(hift_phase_continue_kernel, dim3(H), dim3(256), 0, s, f0, phase, sums, counters, t_a, t_b, H, sr, (float)up, samples);
+    return hipGetLastError() == hipSuccess ? 0 : (set_error("hift_phase_continue launch failed"), -1);
+}
+
+// hift_source_kernel over the absolute samples [n0, n1)
+__global__ void hift_source_window_kernel(const float* f0, const float* phase, const float* table, const float* w, const float* b, float* s_out,
+                                          long long n0, long long n1, int H, int up, float amp, float sigma, float vthr) {
+    const long long n = n0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= n1) return;
+    const int t = (int)(n / up);
+    const float uv = f0[t] > vthr ? 1.0f : 0.0f;
+    const float noise_amp = uv * sigma + ((1.0f - uv) * amp) / 3.0f;
+    float acc = 0.0f;
+    for (int h = 0; h < H; ++h) {
+        const float sine = sinf(phase[(long long)t * H + h]) * amp;
+        const float v = sine * uv + noise_amp * table[n * H + h];
+        acc += v * w[h];
+    }
+    s_out[n - n0] = tanhf(acc + b[0]);
+}
+int launch_hift_source_window(const float* f0, const float* phase, const float* table, const float* w, const float* b, float* s_out,
+                              long long n0, long long n1, int H, int up, float amp, float sigma, float vthr, hipStream_t s) {
+    if (n1 <= n0) return 0;
+    const long long L = n1 - n0;
+    hipLaunchKernelGGL(hift_source_window_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, s, f0, phase, table, w, b, s_out, n0, n1, H, up, amp,
+                       sigma, vthr);
+    return hipGetLastError() == hipSuccess ? 0 : (set_error("hift_source_window launch failed"), -1);
+}
+
 // ---- STFT n_fft=16, hop=4, periodic Hann, center=True / reflect (_stft :491-497) ----------------------------
 __global__ void hift_stft_kernel(const float* x, float* spec, int L, int frames, int ld) {
     __shared__ float cs[16], sn[16], wnd[16];

@@ -164,6 +164,119 @@ int resblock(hipStream_t s, WCursor& wc, bool pp, int L, int C, int k, const int
 
 int expected_weights(const hvx_hift_config& c) { return 5 * 2 + 2 + 2 + 2 + c.n_up * (2 + 2 + 18 + c.n_rb * 18) + 2; }
 
+// ---- streaming vocoder: left context and per-utterance state (include/hvx.h: hvx_hift_stream_*) ---------------------------------------------
+// The derivation of hift.py::hift_left_context, in units of 1 / R of a mel frame (R = prod(up_rates), q_i = R / prod(up_rates[0..i]) = samples at the
+// final rate per sample of stage i).  Kept in step with the Python function by tests/test_gpu_hift_stream.py.
+void left_context(const hvx_hift_config& c, int* f0_frames, int* decode_frames) {
+    *f0_frames = 4 * 2;                                            // condnet.2/4/6/8: k = 3, left pad 2 each; condnet.0 looks right only
+    long long R = 1;
+    for (int i = 0; i < c.n_up; ++i) R *= c.up_rates[i];
+    auto rb = [](int k, const int* d) { long long v = 0; for (int j = 0; j < 3; ++j) v += (long long)(k - 1) * (d[j] + 1); return v; };
+    const long long half = c.n_fft / 2;
+    const long long tail = (half - 1 + c.hop - 1) / c.hop + (c.conv_post_kernel - 1) + 1;     // iSTFT overlap, conv_post, reflection pad (1, 0)
+    long long after = tail, q = 1, best = 0;                       // `after`: everything between the output of stage i and the samples
+    for (int i = c.n_up - 1; i >= 0; --i) {
+        long long main_rb = 0;
+        for (int j = 0; j < c.n_rb; ++j) main_rb = main_rb > rb(c.rb_kernels[j], c.rb_dils[j]) ? main_rb : rb(c.rb_kernels[j], c.rb_dils[j]);
+        const long long src = after + (main_rb + rb(c.src_rb_kernels[i], c.src_rb_dils[i])) * q + (q - 1) + (half + c.hop - 1) / c.hop;
+        best = best > src ? best : src;
+        after += (main_rb + (c.up_kernels[i] - 1) + (c.up_rates[i] - 1)) * q;
+        q *= c.up_rates[i];
+    }
+    best = best > after ? best : after;                            // conv_pre has no left tap
+    *decode_frames = (int)((best + R - 1) / R);
+}
+
+}  // namespace
+
+struct hvx_hift_stream {
+    hvx_hift* h = nullptr;
+    int max_frames = 0;
+    int f0_ctx = 0, dec_ctx = 0;
+    // device (caller's memory, hvx_hift_stream_bind)
+    float* f0 = nullptr;               // [max_frames] final F0 of every frame vocoded so far
+    float* phase = nullptr;            // [max_frames][H]
+    double* sums = nullptr;            // [H] running sums of the phase scan
+    long long* counters = nullptr;     // frames with a final F0, samples handed out
+    const float* table = nullptr;
+    long long table_samples = 0;
+    // test inputs (hvx_hift_stream_set_inputs): F0 of every frame / source of every sample of the utterance, used instead of the predictor / the source stage
+    const float* f0_in = nullptr;
+    const float* source_in = nullptr;
+    // host mirrors
+    int prev_fill = 0, f0_done = 0, decoded = 0;
+    bool finished = false;
+    long long frames_vocoded = 0;
+    long long last[4] = {0, 0, 0, 0};  // the latest piece: first frame and frame count of its decode window, byte offset of its source in the workspace, samples
+};
+
+namespace {
+
+struct Plan {
+    int n = 0, n_f0 = 0, total = 0;        // frames the source / decode see, frames whose F0 is final, frames whose samples are out after this call
+    int f0_w0 = 0, f0_T = 0;               // F0 window [f0_w0, f0_w0 + f0_T) (f0_T = 0: nothing to predict)
+    int ws = 0, T_in = 0, look = 0;        // decode window [ws, ws + T_in) (T_in = 0: nothing to decode)
+    int window = 0;
+    long long samples = 0;
+};
+
+int make_plan(const hvx_hift_stream* st, int fill, int finalize, Plan& p) {
+    const hvx_hift_config& c = st->h->c;
+    const int look = c.conv_pre_kernel - 1, f0_look = 3;
+    if (st->finished) return set_error("hvx_hift_stream: the utterance is final; reset the stream first"), -1;
+    if (fill < st->prev_fill) return set_error("hvx_hift_stream: fill %d is smaller than the previous call's %d", fill, st->prev_fill), -1;
+    if (fill > st->max_frames) return set_error("hvx_hift_stream: fill %d exceeds the stream's %d frames", fill, st->max_frames), -1;
+    if (finalize) {
+        p.n = p.n_f0 = p.total = fill;
+        p.look = 0;
+    } else {
+        p.n = p.n_f0 = fill - f0_look;
+        p.total = p.n - look - 1;
+        p.look = look;
+        if (p.total <= 0) return set_error("hvx_hift_stream: a non-final chunk needs more than %d mel frames", look + 1 + f0_look), -1;
+    }
+    if ((long long)p.n * st->h->up_total > st->table_samples && st->table)
+        return set_error("hvx_hift_stream: %d frames reach past the fixed noise table (%lld samples)", p.n, st->table_samples), -1;
+    p.samples = (long long)(p.total - st->decoded) * st->h->up_total;
+    if (p.n_f0 > st->f0_done) {
+        p.f0_w0 = st->f0_done - st->f0_ctx > 0 ? st->f0_done - st->f0_ctx : 0;
+        p.f0_T = fill - p.f0_w0;
+    }
+    if (p.total > st->decoded) {
+        p.ws = st->decoded - st->dec_ctx > 0 ? st->decoded - st->dec_ctx : 0;
+        p.T_in = p.n - p.ws;
+    }
+    p.window = p.f0_T > p.T_in ? p.f0_T : p.T_in;
+    return 0;
+}
+
+struct StreamBufs {
+    float *f0tmp, *src, *wav;
+};
+size_t carve_stream(const hvx_hift* h, char* base, int window, StreamBufs& sb) {
+    Bufs b;
+    Carve cv(base);
+    cv.off = carve(h, base, window, b);
+    sb.f0tmp = cv.take((size_t)window);
+    sb.src = cv.take((size_t)window * h->up_total);
+    sb.wav = cv.take((size_t)window * h->up_total);
+    return cv.off;
+}
+
+struct StateLayout {
+    size_t f0, phase, sums, counters, total;
+};
+StateLayout state_layout(const hvx_hift* h, int max_frames) {
+    const size_t H = h->c.nb_harmonics + 1;
+    StateLayout l;
+    l.f0 = 0;
+    l.phase = align_up((size_t)max_frames * 4);
+    l.sums = l.phase + align_up((size_t)max_frames * H * 4);
+    l.counters = l.sums + align_up(H * 8);
+    l.total = l.counters + align_up(2 * 8);
+    return l;
+}
+
 }  // namespace
 
 extern "C" {
@@ -198,7 +311,8 @@ size_t hvx_hift_workspace_bytes(const hvx_hift* h, int32_t t) {
     return carve(h, nullptr, t, b) + 256;
 }
 
-int hvx_hift_f0(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, const float* mel, int32_t T, float* f0) {
+// mel: (mel, T) with row stride mel_ld (T for a contiguous plane; the streaming vocoder reads a window of a longer cache plane)
+static int f0_impl(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, const float* mel, int mel_ld, int32_t T, float* f0) {
     hipStream_t s = (hipStream_t)stream;
     const hvx_hift_config& c = h->c;
     Bufs b;
@@ -206,7 +320,7 @@ int hvx_hift_f0(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, const
     WCursor wc{h->w.data(), (int)h->w.size()};
     const int melp = pad32(c.mel), Fp = pad32(c.f0_channels), F = c.f0_channels;
     HIP_OK(hipMemsetAsync(b.melT, 0, (size_t)T * melp * 4, s));
-    HVX_CHECK(launch_transpose_f32(mel, b.melT, c.mel, T, T, melp, s));
+    HVX_CHECK(launch_transpose_f32(mel, b.melT, c.mel, T, mel_ld, melp, s));
     float* cur = b.fa;
     float* nxt = b.fb;
     for (int i = 0; i < 5; ++i) {
@@ -229,6 +343,10 @@ int hvx_hift_f0(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, const
     return 0;
 }
 
+int hvx_hift_f0(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, const float* mel, int32_t T, float* f0) {
+    return f0_impl(h, stream, ws, ws_bytes, mel, T, T, f0);
+}
+
 int hvx_hift_source(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, const float* f0, int32_t T, const float* sine_table,
                     float* source) {
     hipStream_t s = (hipStream_t)stream;
@@ -245,7 +363,8 @@ int hvx_hift_source(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, c
 
 // decode over T_in mel frames of which the last `look` are real right context of conv_pre instead of zero padding (generator.py:674-680,
 // finalize=False): T = T_in - look output frames; the source STFT is taken over all T_in * up samples and cut to 120 T + 1 frames.
-static int decode_impl(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, const float* mel, const float* source, int32_t T_in, int look,
+// mel_ld: row stride of mel (T_in for a contiguous plane).
+static int decode_impl(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, const float* mel, int mel_ld, const float* source, int32_t T_in, int look,
                        float* wav) {
     hipStream_t s = (hipStream_t)stream;
     const hvx_hift_config& c = h->c;
@@ -272,7 +391,7 @@ static int decode_impl(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes
     HVX_CHECK(launch_hift_stft(source, b.spec, (int)((long long)T_in * h->up_total), 32, s));
     // conv_pre (right-looking k) + LeakyReLU(slope) of stage 0
     HIP_OK(hipMemsetAsync(b.melT, 0, (size_t)T_in * melp * 4, s));
-    HVX_CHECK(launch_transpose_f32(mel, b.melT, c.mel, T_in, T_in, melp, s));
+    HVX_CHECK(launch_transpose_f32(mel, b.melT, c.mel, T_in, mel_ld, melp, s));
     float** P = b.pool;
     float* xin = P[0];
     {
@@ -382,11 +501,152 @@ static int decode_impl(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes
 }
 
 int hvx_hift_decode(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, const float* mel, const float* source, int32_t T, float* wav) {
-    return decode_impl(h, stream, ws, ws_bytes, mel, source, T, 0, wav);
+    return decode_impl(h, stream, ws, ws_bytes, mel, T, source, T, 0, wav);
 }
 int hvx_hift_decode_chunk(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, const float* mel, const float* source, int32_t t_in,
                           int32_t look_right, float* wav) {
-    return decode_impl(h, stream, ws, ws_bytes, mel, source, t_in, look_right, wav);
+    return decode_impl(h, stream, ws, ws_bytes, mel, t_in, source, t_in, look_right, wav);
+}
+
+// ---- the per-utterance vocoder stream ----------------------------------------------------------------------------------------------------
+int hvx_hift_left_context(const hvx_hift* h, int32_t* f0_frames, int32_t* decode_frames) {
+    if (!h || !f0_frames || !decode_frames) return set_error("hvx_hift_left_context: null argument"), -1;
+    int a, b;
+    left_context(h->c, &a, &b);
+    *f0_frames = a;
+    *decode_frames = b;
+    return 0;
+}
+
+int64_t hvx_hift_stream_piece_samples(const hvx_hift* h, int32_t prev_fill, int32_t fill, int32_t finalize) {
+    if (!h) return set_error("hvx_hift_stream_piece_samples: null handle"), -1;
+    const int hold = 3 + (h->c.conv_pre_kernel - 1) + 1;           // frames a non-final pass holds back: F0 look-ahead, conv_pre look-ahead, the dropped frame
+    if (prev_fill < 0 || fill < prev_fill) return set_error("hvx_hift_stream_piece_samples: fill %d after %d", fill, prev_fill), -1;
+    if (!finalize && fill - hold <= 0) return set_error("hvx_hift_stream_piece_samples: a non-final chunk needs more than %d mel frames", hold), -1;
+    const long long before = prev_fill - hold > 0 ? prev_fill - hold : 0;
+    const long long total = finalize ? fill : fill - hold;
+    return (int64_t)((total - before) * h->up_total);
+}
+
+int hvx_hift_stream_create(hvx_hift* h, int32_t max_frames, hvx_hift_stream** out) {
+    if (!h || !out || max_frames <= 0) return set_error("hvx_hift_stream_create: null handle or max_frames %d", max_frames), -1;
+    hvx_hift_stream* st = new hvx_hift_stream();
+    st->h = h;
+    st->max_frames = max_frames;
+    left_context(h->c, &st->f0_ctx, &st->dec_ctx);
+    *out = st;
+    return 0;
+}
+void hvx_hift_stream_destroy(hvx_hift_stream* st) { delete st; }
+
+int hvx_hift_stream_reset(hvx_hift_stream* st) {
+    if (!st) return set_error("hvx_hift_stream_reset: null stream"), -1;
+    st->prev_fill = st->f0_done = st->decoded = 0;                 // (the carried sums are not read at frame 0: nothing on the device to clear)
+    st->finished = false;
+    return 0;
+}
+
+size_t hvx_hift_stream_state_bytes(const hvx_hift* h, int32_t max_frames) { return state_layout(h, max_frames).total; }
+
+int hvx_hift_stream_bind(hvx_hift_stream* st, void* state, size_t state_bytes, const float* sine_table, int64_t table_samples) {
+    if (!st || !state || !sine_table) return set_error("hvx_hift_stream_bind: null argument"), -1;
+    const StateLayout l = state_layout(st->h, st->max_frames);
+    if (state_bytes < l.total) return set_error("hvx_hift_stream_bind: state needs %zu bytes, got %zu", l.total, state_bytes), -1;
+    if (((size_t)state & 7) != 0) return set_error("hvx_hift_stream_bind: state must be 8-byte aligned"), -1;
+    char* base = (char*)state;
+    st->f0 = (float*)(base + l.f0);
+    st->phase = (float*)(base + l.phase);
+    st->sums = (double*)(base + l.sums);
+    st->counters = (long long*)(base + l.counters);
+    st->table = sine_table;
+    st->table_samples = table_samples;
+    return 0;
+}
+
+int hvx_hift_stream_set_context(hvx_hift_stream* st, int32_t f0_frames, int32_t decode_frames) {
+    if (!st || f0_frames < 0 || decode_frames < 0) return set_error("hvx_hift_stream_set_context: bad argument"), -1;
+    if (st->prev_fill != 0) return set_error("hvx_hift_stream_set_context: only before the first piece or after a reset"), -1;
+    st->f0_ctx = f0_frames;
+    st->dec_ctx = decode_frames;
+    return 0;
+}
+
+int hvx_hift_stream_set_inputs(hvx_hift_stream* st, const float* f0, const float* source) {
+    if (!st) return set_error("hvx_hift_stream_set_inputs: null stream"), -1;
+    st->f0_in = f0;
+    st->source_in = source;
+    return 0;
+}
+
+size_t hvx_hift_stream_workspace_bytes(const hvx_hift* h, int32_t window_frames) {
+    StreamBufs sb;
+    return carve_stream(h, nullptr, window_frames < 1 ? 1 : window_frames, sb) + 256;
+}
+
+int hvx_hift_stream_plan(const hvx_hift_stream* st, int32_t fill, int32_t finalize, int64_t* out) {
+    if (!st || !out) return set_error("hvx_hift_stream_plan: null argument"), -1;
+    Plan p;
+    HVX_CHECK(make_plan(st, fill, finalize, p));
+    out[0] = p.samples;
+    out[1] = p.window;
+    out[2] = p.T_in;
+    out[3] = p.ws;
+    return 0;
+}
+
+int hvx_hift_stream_info(const hvx_hift_stream* st, int64_t* out) {
+    if (!st || !out) return set_error("hvx_hift_stream_info: null argument"), -1;
+    out[0] = st->prev_fill; out[1] = st->f0_done; out[2] = st->decoded; out[3] = st->frames_vocoded;
+    out[4] = st->last[0]; out[5] = st->last[1]; out[6] = st->last[2]; out[7] = st->last[3];
+    return 0;
+}
+
+int hvx_hift_stream_piece(hvx_hift* h, hvx_stream stream, void* ws, size_t ws_bytes, hvx_hift_stream* st, const float* mel, int32_t mel_ld, int32_t fill,
+                          int32_t finalize, float* wav_out, int64_t wav_cap) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!h || !st || st->h != h) return set_error("hvx_hift_stream_piece: the stream does not belong to this handle"), -1;
+    if (!st->f0 || !st->table) return set_error("hvx_hift_stream_piece: no state bound (hvx_hift_stream_bind)"), -1;
+    const hvx_hift_config& c = h->c;
+    Plan p;
+    HVX_CHECK(make_plan(st, fill, finalize, p));
+    if (fill > 0 && (!mel || mel_ld < fill)) return set_error("hvx_hift_stream_piece: mel plane of row stride %d for %d frames", mel_ld, fill), -1;
+    if (p.samples > wav_cap || (p.samples > 0 && !wav_out)) return set_error("hvx_hift_stream_piece: %lld samples for a buffer of %lld", p.samples, (long long)wav_cap), -1;
+    StreamBufs sb;
+    const int window = p.window < 1 ? 1 : p.window;
+    if (carve_stream(h, (char*)ws, window, sb) > ws_bytes || (p.window > 0 && !ws)) return set_error("hvx_hift_stream_piece: workspace too small"), -1;
+    const int up = h->up_total, H = c.nb_harmonics + 1;
+    // ---- F0 of the newly final frames -> state, then their phase rows from the carried sums
+    if (p.n_f0 > st->f0_done) {
+        const size_t bytes = (size_t)(p.n_f0 - st->f0_done) * 4;
+        if (st->f0_in) {
+            HIP_OK(hipMemcpyAsync(st->f0 + st->f0_done, st->f0_in + st->f0_done, bytes, hipMemcpyDeviceToDevice, s));
+        } else {
+            HVX_CHECK(f0_impl(h, stream, ws, ws_bytes, mel + p.f0_w0, mel_ld, p.f0_T, sb.f0tmp));
+            HIP_OK(hipMemcpyAsync(st->f0 + st->f0_done, sb.f0tmp + (st->f0_done - p.f0_w0), bytes, hipMemcpyDeviceToDevice, s));
+        }
+        HVX_CHECK(launch_hift_phase_continue(st->f0, st->phase, st->sums, st->counters, st->f0_done, p.n_f0, H, c.sampling_rate, up,
+                                             (long long)p.total * up, s));
+    }
+    // ---- source and decode over the window; the first (decoded - ws) frames of its output are left context and stay behind
+    if (p.T_in > 0) {
+        const long long n0 = (long long)p.ws * up, n1 = (long long)p.n * up;
+        if (st->source_in) {
+            HIP_OK(hipMemcpyAsync(sb.src, st->source_in + n0, (size_t)(n1 - n0) * 4, hipMemcpyDeviceToDevice, s));
+        } else {
+            HVX_CHECK(launch_hift_source_window(st->f0, st->phase, st->table, (const float*)h->w[12], (const float*)h->w[13], sb.src, n0, n1, H, up,
+                                                c.nsf_alpha, c.nsf_sigma, c.voiced_threshold, s));
+        }
+        HVX_CHECK(decode_impl(h, stream, ws, ws_bytes, mel + p.ws, mel_ld, sb.src, p.T_in, p.look, sb.wav));
+        HIP_OK(hipMemcpyAsync(wav_out, sb.wav + (long long)(st->decoded - p.ws) * up, (size_t)p.samples * 4, hipMemcpyDeviceToDevice, s));
+        st->frames_vocoded += p.T_in;
+        st->last[0] = p.ws; st->last[1] = p.T_in; st->last[2] = (long long)((char*)sb.src - (char*)ws);
+    }
+    st->last[3] = p.samples;
+    st->prev_fill = fill;
+    st->f0_done = p.n_f0 > st->f0_done ? p.n_f0 : st->f0_done;
+    st->decoded = p.total;
+    st->finished = finalize != 0;
+    return 0;
 }
 
 }  // extern "C"

@@ -311,6 +311,13 @@ int launch_hift_phase(const float* f0, float* phase, int T, int H, float sr, int
 // per-sample source (generator.py:289-317, 358-375): s[n] = tanh( sum_h w[h]*(sin(phase[t][h])*amp*uv + namp*table[n][h]) + b )
 int launch_hift_source(const float* f0, const float* phase, const float* table, const float* w, const float* b, float* s_out,
                        int T, int H, int up, float amp, float sigma, float vthr, hipStream_t s);
+// the streaming vocoder (hvx_hift_stream_piece): the phase scan continued over frames [t_a, t_b) from the double sums carried in sums[H] (read when
+// t_a > 0, rewritten with the sums after frame t_b - 1); f0 / phase are the stream state's arrays, indexed by absolute frame; counters[0..1] = t_b, samples
+int launch_hift_phase_continue(const float* f0, float* phase, double* sums, long long* counters, int t_a, int t_b, int H, float sr, int up,
+                               long long samples, hipStream_t s);
+// ... and the source of the absolute samples [n0, n1) from those arrays, table[n][h] addressed by absolute sample; s_out[n - n0]
+int launch_hift_source_window(const float* f0, const float* phase, const float* table, const float* w, const float* b, float* s_out,
+                              long long n0, long long n1, int H, int up, float amp, float sigma, float vthr, hipStream_t s);
 // STFT n_fft=16 hop=4 hann, center/reflect (generator.py:491-497): spec[f][0..8]=re, [9..17]=im, row stride ld (>=18, rest zero)
 int launch_hift_stft(const float* s_in, float* spec, int L, int ld, hipStream_t s);
 // x[f][0..8] -> mag=exp clip 1e2, x[f][9..17] -> phase=sin; iSTFT; clamp (generator.py:702-710, 499-505)

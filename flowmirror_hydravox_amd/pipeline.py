@@ -100,7 +100,8 @@ class _StreamUtterance:
     as state the batched acoustic stage can work on — the mel cache plane (sized from the utterance's token budget; `fill` frames are valid), the chunk
     schedule, the prompt arguments of the flow, the jobs that are ready and `handed`, the samples already handed out."""
 
-    def __init__(self, u, flow, hop, max_tokens, device, t_fetch):
+    def __init__(self, u, flow, hop, max_tokens, device, t_fetch, hift=None):
+        """hift: given with serve(incremental_vocoder=True) — the utterance owns a vocoder stream (hift.HiftStream) as long as its mel cache plane"""
         from .streaming import ChunkSchedule
         pt = _flow_prompt(u)
         self.u = u
@@ -113,11 +114,18 @@ class _StreamUtterance:
         self.cache = torch.empty(flow.output_size, max(1, int(max_tokens)) * flow.token_mel_ratio, dtype=torch.float32, device=device)
         self.fill = 0
         self.handed = 0
+        self.vstream = None if hift is None else hift.stream(min(int(self.cache.shape[1]), hift.max_stream_frames))
         self.jobs = []                   # (tokens in the piece, covered, final) not yet solved, in order
         self.pieces = 0
         self.tokens = None               # the utterance's full token list, once the LM has finished it
         self.t_fetch = t_fetch
         self.dead = False                # cancelled by its caller: nothing more of it is solved; it leaves when the LM hands it back
+
+    def release(self):
+        """the utterance leaves (final piece, cancelled, dropped, abandoned): its vocoder stream goes with its mel cache plane"""
+        if self.vstream is not None:
+            self.vstream.close()
+            self.vstream = None
 
     def flow_inputs(self, flow, n, final):
         """mu, spk, cond of the flow over the prompt and the first n generated tokens (HvxFlow.inference's plumbing)"""
@@ -343,7 +351,7 @@ class HvxPipeline:
     @torch.inference_mode()
     def serve(self, source, lm_slots=16, acoustic_batch=None, acoustic_min_batch=1, max_out=None, max_prefix=None,
               max_token_text_ratio=20, min_token_text_ratio=2, pace=None, mixed_sampling=False, win_cap=None, mixed_heads=False, head_cap=None,
-              stream=False, sync_every=None, event_log=None):
+              stream=False, sync_every=None, event_log=None, incremental_vocoder=False):
         """The continuous engine over an open-ended SOURCE of utterances: `source.poll(block)` returns the next `Utterance`, or None when
         nothing is waiting (it is asked to block only while the decode grid is idle), and raises StopIteration when closed.  Generator over
         (utterance, waveform | exception, tokens) in completion order.
@@ -374,6 +382,10 @@ class HvxPipeline:
         utterance's fetch to its first piece) of the latest 4096 utterances, n = fetch order) and `pieces_out` (pieces already handed out, per entry of
         `abandoned`).  `event_log`: a list (or anything with append) that receives the engine's log as it happens — ('tokens', n, count) / ('done', n)
         from the LM thread, ('piece', n, index, final) from this one; nothing is logged without it (a server's serve() call may live for days).
+        `incremental_vocoder` (with `stream`; ValueError without): every utterance owns a vocoder stream (hift.HiftStream) sized like its mel cache plane and a
+        piece is vocoded from a window of the cache — left context + new frames + look-ahead — instead of the whole cache; pieces, order, `index` and `final`
+        are those of the switch-off path.  The stream is released with the plane (final piece, cancel, drop, abandoned).  `last_continuous['vocoder_frames']`:
+        mel frames the vocoder decoded over the call, with the switch on or off.
         `sync_every`: decode steps per host round trip of the grid (default 8); smaller: tokens — and so pieces — surface at a finer cadence, for more
         round trips.
         Cancelling ONE utterance: `Utterance.cancel` (any object with is_set()) goes to the decode engine with the request (HvxLLM.generate_stream).  Unstreamed, a
@@ -383,6 +395,8 @@ class HvxPipeline:
         acoustic_batch = acoustic_batch or self.acoustic_batch
         acoustic_min_batch = max(1, min(int(acoustic_min_batch), acoustic_batch))
         piecewise = bool(stream)                           # (`stream` names the acoustic stage's device stream below)
+        if incremental_vocoder and not piecewise:
+            raise ValueError('incremental_vocoder needs stream=True: an unstreamed utterance is vocoded once')
         import queue
         import threading
         if getattr(self, '_bg_stream', None) is None:
@@ -428,7 +442,8 @@ class HvxPipeline:
         from collections import deque
         fetched = {}                                       # stream: running id -> (time of its fetch, tokens its mel cache must hold), until its session exists
         live = {}                                          # stream: running id -> _StreamUtterance, until its final piece has left
-        acct = dict(pieces=0, chunk_solves=0, first=deque(maxlen=4096), acoustic=0.0, audio=0.0, tokens=0, cancelled=0, with_cancel=False)
+        acct = dict(pieces=0, chunk_solves=0, first=deque(maxlen=4096), acoustic=0.0, audio=0.0, tokens=0, cancelled=0, with_cancel=False, vocoder_frames=0,
+                    incremental=bool(incremental_vocoder))
 
         class _Requests:
             @staticmethod
@@ -562,8 +577,10 @@ class HvxPipeline:
             if acct['with_cancel']:                                # (a run in which no utterance carried `cancel` reports what it always reported)
                 self.last_continuous['cancelled'] = acct['cancelled']
             if piecewise:
+                for se in live.values():                            # (utterances the run leaves behind: abandoned, or cut off by an error)
+                    se.release()
                 self.last_continuous.update(tokens=acct['tokens'], audio_seconds=acct['audio'], acoustic_seconds=acct['acoustic'], pieces=acct['pieces'],
-                                            chunk_solves=acct['chunk_solves'], first_piece_seconds=list(acct['first']),
+                                            chunk_solves=acct['chunk_solves'], first_piece_seconds=list(acct['first']), vocoder_frames=acct['vocoder_frames'],
                                             pieces_out=[0] * len(abandoned) + [live[k].pieces if k in live else 0 for k in seen])
 
     def _stream_consumer(self, q, seen, fetched, live, flow, hift, stream, acoustic_batch, acct, event_log, max_pad=0.15):
@@ -579,12 +596,14 @@ class HvxPipeline:
             if n not in live:
                 t_fetch, budget = fetched.pop(n)
                 with _on(stream):                                  # (its copies to the device are ordered with the solves that read them)
-                    live[n] = _StreamUtterance(seen[n], flow, hop, budget, self.device, t_fetch)
+                    live[n] = _StreamUtterance(seen[n], flow, hop, budget, self.device, t_fetch, hift=hift if acct['incremental'] else None)
             return live[n]
 
         def drop(n):
             """utterance n leaves without (further) pieces: its session, its bookkeeping and whatever of it was scheduled"""
-            live.pop(n, None)
+            se = live.pop(n, None)
+            if se is not None:
+                se.release()
             fetched.pop(n, None)
             order[:] = [m for m in order if m != n]
 
@@ -672,8 +691,14 @@ class HvxPipeline:
                         for n, f in zip(bucket, fresh):
                             se = live[n]
                             se.fill += f
-                            wav, _ = hift.inference(speech_feat=se.cache[None, :, :se.fill], finalize=final)
-                            piece = wav[0, se.handed:]
+                            if se.vstream is not None:
+                                before = se.vstream.frames_vocoded
+                                piece = se.vstream.piece(se.cache, se.fill, final)[0]
+                                acct['vocoder_frames'] += se.vstream.frames_vocoded - before
+                            else:
+                                wav, _ = hift.inference(speech_feat=se.cache[None, :, :se.fill], finalize=final)
+                                piece = wav[0, se.handed:]
+                                acct['vocoder_frames'] += se.fill
                             se.handed += piece.numel()
                             out.append((n, piece, final))
                 stream.synchronize()
@@ -690,6 +715,7 @@ class HvxPipeline:
                 if final:
                     info['tokens'] = se.tokens
                     acct['tokens'] += len(se.tokens)
+                    se.release()
                     del live[n]
                     u = seen.pop(n)
                 else:

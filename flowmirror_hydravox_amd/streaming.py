@@ -18,8 +18,13 @@ class StreamSession:
     been handed to the caller.  Every push = flow over the token prefix -> keep only the frames past the prefix already covered ->
     vocode ALL frames so far -> return the samples not yet handed out."""
 
-    def __init__(self, flow, hift, prompt_token, prompt_feat, embedding, device=None):
+    def __init__(self, flow, hift, prompt_token, prompt_feat, embedding, device=None, incremental_vocoder=False, max_frames=None):
+        """incremental_vocoder: the session owns a vocoder stream (`hift.stream(max_frames)`, hift.HiftStream) and every push vocodes a window of the
+        cached mel — left context + new frames + look-ahead — instead of all of it; the samples are those of the whole-cache pass.  max_frames:
+        the longest utterance the stream holds (default: what the vocoder's fixed noise table covers, `hift.max_stream_frames`).  The stream is
+        released with the final push (or close())."""
         self.flow, self.hift = flow, hift
+        self._vstream = hift.stream(int(max_frames) if max_frames is not None else hift.max_stream_frames) if incremental_vocoder else None
         self.device = device if device is not None else getattr(flow, 'device', 'cpu')
         self.embedding = embedding.to(self.device)
         prompt_token, prompt_feat = prompt_token.to(self.device), prompt_feat.to(self.device)
@@ -53,8 +58,20 @@ class StreamSession:
                 raise AssertionError('speed change only support non-stream inference mode')      # cli/model.py:425
             from .ops import resample_linear                                                      # F.interpolate(mode='linear') in libhvx
             mel = resample_linear(mel, int(mel.shape[2] / speed))
+        if self._vstream is not None and speed == 1.0:
+            out = self._vstream.piece(mel, mel.shape[2], finalize)
+            self._handed += out.shape[1]
+            if finalize:
+                self.close()
+            return out
         wav, _ = self.hift.inference(speech_feat=mel, finalize=finalize)
         return self._unheard(wav)
+
+    def close(self):
+        """release the vocoder stream (the final push does it; a session that is abandoned earlier calls this)"""
+        if self._vstream is not None:
+            self._vstream.close()
+            self._vstream = None
 
     # the reference's name and argument order (cli/model.py:405)
     def token2wav(self, token, token_offset, stream=False, finalize=False, speed=1.0):
@@ -96,15 +113,26 @@ class ChunkSchedule:
         return len(self.tokens), self.covered
 
 
-def stream_tts(token_source, flow, hift, prompt_token, prompt_feat, embedding, token_hop_len=25, stream=True, speed=1.0):
+def stream_tts(token_source, flow, hift, prompt_token, prompt_feat, embedding, token_hop_len=25, stream=True, speed=1.0, incremental_vocoder=False):
     """Generator of waveform pieces (1, L) float32 from an iterable of speech-token ids (e.g. `HvxLLM.inference(...)`).
 
     The chunk schedule is the reference's (cli/model.py:329-352), kept in `ChunkSchedule`: the first hop is padded so that prompt + hop is a whole number
     of `token_hop_len` chunks (`prompt_token_pad`), a chunk is synthesised as soon as `hop + pre_lookahead_len` unseen tokens are
     buffered, and whatever remains when the LM stops goes through once more with `finalize=True`.  `token_hop_len` must be
     `static_chunk_size / token_mel_ratio` ("must matching training static_chunk_size", cli/model.py:395-396).
+    incremental_vocoder: every piece is vocoded from a window of the mel cache and the session's vocoder stream (StreamSession); same pieces.  It
+    needs stream=True (ValueError otherwise: an unstreamed utterance is vocoded once).
     """
-    sess = StreamSession(flow, hift, prompt_token, prompt_feat, embedding)
+    if incremental_vocoder and not stream:
+        raise ValueError('incremental_vocoder needs stream=True: an unstreamed utterance is vocoded once')
+    sess = StreamSession(flow, hift, prompt_token, prompt_feat, embedding, incremental_vocoder=incremental_vocoder)
+    try:
+        yield from _stream_tts(sess, token_source, flow, prompt_token, token_hop_len, stream, speed)
+    finally:
+        sess.close()                                 # (a consumer that stops early leaves no vocoder stream behind)
+
+
+def _stream_tts(sess, token_source, flow, prompt_token, token_hop_len, stream, speed):
     if not stream:
         tokens = [int(t) for t in token_source]
         yield sess.token2wav(torch.tensor(tokens, dtype=torch.int32).unsqueeze(0), 0, stream=False, finalize=True, speed=speed)

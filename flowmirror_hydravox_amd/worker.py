@@ -390,7 +390,7 @@ class _TaskSource:
 
 
 def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_id, frontend_factory=None, lm_slots=None, acoustic_batch=4,
-                               mixed_sampling=False, mixed_heads=False, stream=False, segment_fanout=False):
+                               mixed_sampling=False, mixed_heads=False, stream=False, segment_fanout=False, incremental_vocoder=False):
     """Same wire format as worker_process_tts, served by the continuous-batching engine (replaces the one-request-at-a-time
     loop of server/worker.py:54-102 and what server/router.py:144-156 feeds it): `tts` / `zero_shot` tasks join ONE decode grid as they arrive
     (HvxPipeline.serve -> HvxLLM.generate_stream: the LM weights are streamed once per step for every request in flight, a finished request's
@@ -401,6 +401,7 @@ def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_
     another inference_head_num, a window over 64 (or 0) and the non-synthesis tasks remain epoch boundaries.
     mixed_heads=True: requests with different inference_head_num share the grid as well (rows per sequence: the model's head_num).
     stream=True: one result message per audio PIECE (see serve_queue).
+    incremental_vocoder=True (with stream=True): the pieces come from a per-request vocoder stream instead of a pass over the whole mel cache (see serve_queue).
     segment_fanout=True: a `tts` task over 5000 characters no longer drains the grid: its segments are utterances of the running epoch (see serve_queue)."""
     os.environ['CUDA_VISIBLE_DEVICES'] = str(worker_id % num_workers_gpu)
     from .model_manager import HvxModelManager
@@ -411,11 +412,12 @@ def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_
     mm.load_models(argparse.Namespace(config=os.getenv('TTS_CONFIG'), model_dir=os.getenv('TTS_MODEL_DIR'), bf16=_env_flag('TTS_BF_16'),
                                       fp16=_env_flag('TTS_FP_16'), cpu=_env_flag('TTS_CPU', False)))
     serve_queue(mm, task_queue, result_dict, worker_id, lm_slots=lm_slots, acoustic_batch=acoustic_batch, mixed_sampling=mixed_sampling,
-                mixed_heads=mixed_heads, **(dict(stream=True) if stream else {}), **(dict(segment_fanout=True) if segment_fanout else {}))
+                mixed_heads=mixed_heads, **(dict(stream=True) if stream else {}), **(dict(segment_fanout=True) if segment_fanout else {}),
+                **(dict(incremental_vocoder=True) if incremental_vocoder else {}))
 
 
 def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acoustic_batch=4, normalise=None, mixed_sampling=False, win_cap=64, token_log=None,
-                mixed_heads=False, head_cap=None, stream=False, segment_fanout=False, segmented_text_chars=None):
+                mixed_heads=False, head_cap=None, stream=False, segment_fanout=False, segmented_text_chars=None, incremental_vocoder=False):
     """the loop of worker_process_tts_batched over an already loaded model manager (tests drive this directly).  Returns its counters:
     `epochs` (decode grids started) and `epoch_boundaries` (tasks that closed a running grid because they could not join it; the shutdown
     sentinel is not one).  token_log: a dict that receives task id -> speech-token ids of every synthesised request.
@@ -423,6 +425,8 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
     stream=True: HvxPipeline.serve(stream=True) — every audio piece of a request is a result message of its own, written the moment the piece exists under
     the key stream_result_key(task id, piece_index): the keys of an unstreamed result (`output_audio` = this piece's samples, `duration` = this piece's) plus
     `piece_index` and `final`.  A request that fails is answered once, under its task id, as without the switch.
+    incremental_vocoder=True: HvxPipeline.serve(stream=True, incremental_vocoder=True) — same messages, the vocoder works on a window per piece (hift.HiftStream);
+    without stream=True it is refused with a ValueError before anything is served.
     segment_fanout=True: a `tts` task over `segmented_text_chars` characters (None: model_manager.SEGMENTED_TEXT_CHARS) that can join an epoch is served as
     its segments in the decode grid (_TaskSource) instead of one by one between two epochs.  When the last segment has its waveform, ONE result is written
     under the task id: the keys of text_to_speech's segmented result, `output_audio` = the segments in text order with the zero gaps between them.  The first
@@ -433,6 +437,8 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
     A task {'task_type': 'cancel', 'id': c, 'target_id': x} is honoured inside a running epoch without closing it (_TaskSource); outside one it is answered
     {'cancelled': False}.  Counters: `fanned_out` (tasks expanded) and `cancelled` (cancel tasks honoured)."""
     from collections import deque
+    if incremental_vocoder and not stream:
+        raise ValueError('incremental_vocoder needs stream=True: an unstreamed request is vocoded once')
     stats = dict(epochs=0, epoch_boundaries=0, mixed_sampling=bool(mixed_sampling), mixed_heads=bool(mixed_heads), fanned_out=0, cancelled=0)
     backlog = deque()                                  # the one task a source read past while segments were waiting (it was looking for cancel tasks): served before the queue
     fan_kw = dict(segment_fanout=bool(segment_fanout), segmented_text_chars=segmented_text_chars, backlog=backlog)
@@ -479,6 +485,8 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
                 kw.update(mixed_heads=True, head_cap=head_cap)
             if stream:
                 kw.update(stream=True)
+            if incremental_vocoder:
+                kw.update(incremental_vocoder=True)
             for u, wav, toks in pipe.serve(_Tracked(src, in_flight), lm_slots=lm_slots, acoustic_batch=acoustic_batch, acoustic_min_batch=1, **kw):
                 t = u.tag
                 if getattr(u, 'segment', None) is not None:     # a segment of a fanned-out task

@@ -499,6 +499,43 @@ int hvx_hift_decode(hvx_hift* h, hvx_stream s, void* ws, size_t ws_bytes, const 
 int hvx_hift_decode_chunk(hvx_hift* h, hvx_stream s, void* ws, size_t ws_bytes, const float* mel, const float* source, int32_t t_in,
                           int32_t look_right, float* wav);
 
+/* ---- streaming vocoder: one stream per utterance (additive at ABI 8; a binding that wants these symbols checks for them) ----
+ * A stream carries what the causal generator remembers of an utterance: the final F0 of every frame vocoded so far, the per-frame
+ * harmonic phase rows, the double-precision running sums of the phase scan and the frame / sample counters (device memory of the caller,
+ * hvx_hift_stream_state_bytes / hvx_hift_stream_bind; a few tens of bytes per frame).  hvx_hift_stream_piece then vocodes a WINDOW of the
+ * utterance's mel cache (left context + new frames + look-ahead) and returns exactly the samples that a pass over the whole cache
+ * would add: hvx_hift_f0 + hvx_hift_source + hvx_hift_decode[_chunk] over cache[:, :fill], cut at the samples already handed out.
+ * hvx_hift_left_context: the left context as a function of the configuration (hift.py::hift_left_context states the derivation):
+ * f0_frames earlier mel frames per F0 value, decode_frames earlier mel frames (and their source samples) per decoded sample. */
+typedef struct hvx_hift_stream hvx_hift_stream;
+int hvx_hift_left_context(const hvx_hift* h, int32_t* f0_frames, int32_t* decode_frames);
+/* samples a piece call adds, from (previous fill, fill, finalize): non-final passes hand out (fill - 3 - conv_pre_look_right - 1) * up samples in
+ * total, the final one fill * up.  -1 (hvx_last_error) where hvx_hift_stream_piece would refuse the pair.  Host arithmetic only. */
+int64_t hvx_hift_stream_piece_samples(const hvx_hift* h, int32_t prev_fill, int32_t fill, int32_t finalize);
+int hvx_hift_stream_create(hvx_hift* h, int32_t max_frames, hvx_hift_stream** out);       /* host state only: nothing is allocated on the device */
+void hvx_hift_stream_destroy(hvx_hift_stream* st);
+int hvx_hift_stream_reset(hvx_hift_stream* st);                                           /* a new utterance in the same memory */
+size_t hvx_hift_stream_state_bytes(const hvx_hift* h, int32_t max_frames);
+/* state: device memory of hvx_hift_stream_state_bytes (8-byte aligned, F0 array first); sine_table f32 [table_samples][H] as in hvx_hift_source */
+int hvx_hift_stream_bind(hvx_hift_stream* st, void* state, size_t state_bytes, const float* sine_table, int64_t table_samples);
+/* tests: another left context (before the first piece), and the F0 of every frame / the source of every sample of the utterance as device
+ * arrays that replace the predictor / the source stage (NULL: the stage runs) */
+int hvx_hift_stream_set_context(hvx_hift_stream* st, int32_t f0_frames, int32_t decode_frames);
+int hvx_hift_stream_set_inputs(hvx_hift_stream* st, const float* f0, const float* source);
+size_t hvx_hift_stream_workspace_bytes(const hvx_hift* h, int32_t window_frames);         /* a function of the window alone, not of max_frames */
+/* what hvx_hift_stream_piece(fill, finalize) would do next: out[0] samples it adds, out[1] window_frames of its workspace, out[2] / out[3] frames and
+ * first frame of its decode window.  -1 where the piece call refuses. */
+int hvx_hift_stream_plan(const hvx_hift_stream* st, int32_t fill, int32_t finalize, int64_t* out);
+/* out[0..3]: previous fill, frames with a final F0, frames handed out, frames decoded so far (summed over the calls since create);
+ * out[4..7]: the latest piece's decode window (first frame, frames), the byte offset of its source samples in the workspace, its samples */
+int hvx_hift_stream_info(const hvx_hift_stream* st, int64_t* out);
+/* mel: the utterance's f32 mel cache plane (mel, mel_ld) with `fill` valid frames; wav_out receives the new samples (hvx_hift_stream_plan /
+ * hvx_hift_stream_piece_samples say how many).  Refused with -1 before anything is launched: fill below the previous call's or above max_frames, a
+ * call after a final one without a reset, a non-final fill of at most 3 + conv_pre_look_right + 1 frames, wav_cap too small, frames past the
+ * noise table.  A window that starts at frame 0 issues the launches of the whole-cache pass. */
+int hvx_hift_stream_piece(hvx_hift* h, hvx_stream s, void* ws, size_t ws_bytes, hvx_hift_stream* st, const float* mel, int32_t mel_ld, int32_t fill,
+                          int32_t finalize, float* wav_out, int64_t wav_cap);
+
 /* ---------------------------------------------------------------------------------------------------
  * Matcha-TTS family, fp32:
  *   hvx_matcha_*   — matcha/models/components/decoder.py:363-443 Decoder.forward (and its CosyVoice variant

@@ -6,6 +6,8 @@ Prints time to first audio and the arrival time / length of every piece; full-si
     python tools/bench_stream.py --serve 8 --slots 8 [--chars 128]     # N concurrent streamed requests through HvxPipeline.serve(stream=True): first-audio
                                                                        # time and piece inter-arrival per request, and the tokens/s of the same requests
                                                                        # with stream=False (what streaming costs under load)
+    python tools/bench_stream.py --incremental-vocoder [--serve 8 --slots 8]   # the vocoder on a window per piece (hift.HiftStream) against the whole-cache pass, both
+                                                                       # settings in this process: per-piece arrival times, acoustic seconds, vocoder_frames
 """
 import argparse
 import os
@@ -38,6 +40,8 @@ def serve_bench(a):
         def poll(self, block):
             return next(self.it)
     kw = dict(lm_slots=a.slots, max_out=n_spk, max_prefix=2 + a.chars + 20 + a.prompt, **(dict(sync_every=a.sync_every) if a.sync_every else {}))
+    if a.incremental_vocoder:
+        return serve_ab(a, cfg, pipe, Src, kw, n_spk)
     for rep in range(2):                                        # first pass warms up (graph capture, workspaces)
         torch.cuda.synchronize()
         t0 = time.time()
@@ -72,6 +76,61 @@ def serve_bench(a):
               % (plain['tokens'], t_plain, plain['tokens'] / t_plain, (lc['tokens'] / t_stream) / (plain['tokens'] / t_plain)))
 
 
+def serve_ab(a, cfg, pipe, Src, kw, n_spk):
+    """serve(stream=True) with incremental_vocoder off and on, same requests, one process: arrival time of every piece, acoustic seconds, vocoder_frames"""
+    res = {}
+    for rep in range(2):                                        # first pass warms up (graph capture, workspaces)
+        for on in (False, True):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            arr = {}
+            for u, piece, info in pipe.serve(Src(), stream=True, incremental_vocoder=on, **kw):
+                if isinstance(piece, BaseException):
+                    raise piece
+                piece = piece.cpu()
+                arr.setdefault(u.seed, []).append(time.time() - t0)
+            res[on] = (arr, time.time() - t0, dict(pipe.last_continuous))
+    print('serve A/B: %d requests of %d tokens in %d slots; incremental_vocoder off | on' % (a.serve, n_spk, a.slots))
+    for on in (False, True):
+        arr, t, lc = res[on]
+        print('  %s: %d pieces, %.3f s wall, acoustic %.3f s, vocoder_frames %d, audio %.2f s, %.0f tokens/s'
+              % ('on ' if on else 'off', lc['pieces'], t, lc['acoustic_seconds'], lc['vocoder_frames'], lc['audio_seconds'], lc['tokens'] / t))
+    for seed in sorted(res[False][0]):
+        print('  request %d piece arrival [s] off: %s' % (seed, ' '.join('%.3f' % x for x in res[False][0][seed])))
+        print('  request %d piece arrival [s] on : %s' % (seed, ' '.join('%.3f' % x for x in res[True][0][seed])))
+    print('  acoustic seconds on / off = %.3f; vocoder_frames on / off = %.3f'
+          % (res[True][2]['acoustic_seconds'] / res[False][2]['acoustic_seconds'], res[True][2]['vocoder_frames'] / float(res[False][2]['vocoder_frames'])))
+
+
+def vocoder_ab(a, cfg, pipe):
+    """the vocoder alone over one utterance's worth of mel frames delivered in pieces of `static_chunk_size` frames: device time per piece, whole-cache pass
+    against HiftStream (random mel: the arithmetic does not depend on the values)"""
+    hop = cfg.flow.static_chunk_size
+    n = 2 * int(a.chars * 5.5)
+    mel = torch.randn(1, 80, n, generator=torch.Generator().manual_seed(0)).to('cuda')
+    fills = [(f, False) for f in range(hop, n, hop)] + [(n, True)]
+    out = {}
+    for on in (False, True):
+        for rep in range(2):
+            st = pipe.hift.stream(n) if on else None
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(fills) + 1)]
+            ev[0].record()
+            for i, (f, fin) in enumerate(fills):
+                if on:
+                    st.piece(mel, f, fin)
+                else:
+                    pipe.hift.inference(speech_feat=mel[:, :, :f], finalize=fin)
+                ev[i + 1].record()
+            torch.cuda.synchronize()
+            out[on] = ([ev[i].elapsed_time(ev[i + 1]) for i in range(len(fills))], st.frames_vocoded if on else sum(f for f, _ in fills))
+            if on:
+                st.close()
+    print('vocoder alone: %d frames in %d pieces of %d' % (n, len(fills), hop))
+    for on in (False, True):
+        ms, frames = out[on]
+        print('  %s: %.2f ms in all, frames decoded %d; per piece [ms]: %s' % ('on ' if on else 'off', sum(ms), frames, ' '.join('%.2f' % x for x in ms)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--chars', type=int, default=128)
@@ -81,6 +140,7 @@ def main():
     ap.add_argument('--serve', type=int, default=0, help='N concurrent requests through the continuous-batching server, streamed and unstreamed')
     ap.add_argument('--slots', type=int, default=8, help='decode-grid slots of --serve')
     ap.add_argument('--sync-every', type=int, default=None, help='decode steps per host round trip of --serve (default 8)')
+    ap.add_argument('--incremental-vocoder', action='store_true', help='A/B of the windowed vocoder (hift.HiftStream) against the whole-cache pass, in one process')
     a = ap.parse_args()
     if a.serve:
         return serve_bench(a)
@@ -102,20 +162,22 @@ def main():
                                   prompt_speech_token_len=torch.tensor([a.prompt], dtype=torch.int32), embedding=u.embedding[None],
                                   max_token_text_ratio=ratio, min_token_text_ratio=ratio, seed=0)
 
+    if a.incremental_vocoder:
+        vocoder_ab(a, cfg, pipe)
     for rep in range(2):                                        # first pass warms up (graph capture, workspaces)
-        for stream in (True, False):
+        for stream, inc in ((True, False), (True, True), (False, False)) if a.incremental_vocoder else ((True, False), (False, False)):
             torch.cuda.synchronize()
             t0 = time.time()
             arr = []
             for wav in stream_tts(tokens(), pipe.flow, pipe.hift, u.prompt_speech_token[None], u.prompt_feat[None], u.embedding[None],
-                                  token_hop_len=cfg.flow.static_chunk_size // cfg.flow.token_mel_ratio, stream=stream):
+                                  token_hop_len=cfg.flow.static_chunk_size // cfg.flow.token_mel_ratio, stream=stream, **(dict(incremental_vocoder=True) if inc else {})):
                 wav = wav.cpu()
                 arr.append((time.time() - t0, wav.shape[1] / cfg.sample_rate))
             if rep == 0:
                 continue
             audio = sum(x[1] for x in arr)
             print('%s: %d pieces, first audio after %.3f s (%.2f s of audio), all %.2f s of audio after %.3f s (RTF %.4f)'
-                  % ('stream   ' if stream else 'one piece', len(arr), arr[0][0], arr[0][1], audio, arr[-1][0], arr[-1][0] / audio))
+                  % (('stream+inc' if inc else 'stream   ') if stream else 'one piece', len(arr), arr[0][0], arr[0][1], audio, arr[-1][0], arr[-1][0] / audio))
             if stream:
                 print('  piece arrival [s]: ' + ' '.join('%.2f' % x[0] for x in arr))
                 late = [i for i in range(1, len(arr)) if arr[i][0] > arr[0][0] + sum(x[1] for x in arr[:i])]
