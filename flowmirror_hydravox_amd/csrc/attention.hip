@@ -384,11 +384,9 @@ __global__ void attn_combine_kernel(AttnArgs a) {
 // online-softmax loop below (FAST = false path; exercised by tests/test_gpu_ops.py::test_attention_dit_fallback_on_score_spike).
 // PRE: the query operand already carries scale * log2(e) (a.q_log2: written that way by the fused QKV epilogue, one rounding) — the MFMA
 // accumulator then starts at -m_ref and exp2 is the only arithmetic left per score.  Otherwise the scale is applied to the fp32 score.
-// LAB (tools/attn_probe.py with option attn_lab = n, library built with -DHVX_LAB): timing-only variants that REMOVE one ingredient of the fast loop
-// each (results are garbage): 1 no global loads / LDS stash of the next tile, 2 no barrier, 4 K / V^T fragments from registers instead of LDS,
-// 8 no exp2 / bf16 conversion, 16 no MFMA.  0 = the product.
-// NW: waves per workgroup.  4: 64 QR rows per workgroup, two workgroups per CU.  8: 128 QR rows per workgroup, ONE per CU — the same two waves per SIMD,
-// but a K / V^T tile is staged once for twice the rows, so every thread moves half the bytes per tile (one 16-byte piece of K and one of V^T).
+// Four waves per workgroup: 64 QR rows per workgroup, two workgroups per CU.  (Measured and dropped, round 5: eight waves, 128 QR rows, ONE workgroup per CU — a K / V^T
+// tile staged once for twice the rows — 1158 vs 1055 us at B = 8, 349 vs 275 us at B = 2: the barrier over eight waves costs more than the halved staging saves; two
+// independent 4-wave workgroups per CU drift apart and cover each other.)
 // ROT 1 (round 6; the default where it exists: 64-row waves, pre-scaled queries, no chunk mask): the in-wave pipeline ROTATED ACROSS key tiles.  Every step of the loop is
 // QK(i + 1) + SM(i) + PV(i - 1) — 18 MFMAs against 16 exponentials + 8 conversions — including the tile boundary (QK(0) of tile t + 1 beside SM(3) and PV(2) of tile t; PV(3)
 // of tile t beside QK(1) / SM(0) of tile t + 1), where the in-tile pipeline above runs 8 bare QK MFMAs at the head and 10 bare PV MFMAs at the tail of every tile and packs the
@@ -397,9 +395,9 @@ __global__ void attn_combine_kernel(AttnArgs a) {
 // are re-filled in place one MFMA pair behind their last use (K(t + 1) during QK(3, t), V(t) during PV(3, t - 1)), so the working set is the in-tile form's — minus the 16
 // registers of the per-row reference, which this form drops (scores start from 0; see the step's comment and the vote after the loop): with them the loop spills.
 // Measured at B = 8, H = 16, T = 5632: 849 against 967 us (profiles/r06_attn_tile_ab.md), flow solve 398.7 against 419.6 ms.
-template <int QR, bool FAST, bool PRE, int LAB = 0, int NW = 4, int ROT = 0, class T = bf16_t>   // 16-row query tiles per wave: every K / V^T fragment read from LDS feeds QR MFMAs
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(AttnArgs a) {
-    static_assert(ROT == 0 || (QR == 4 && FAST && PRE && LAB == 0 && NW == 4), "the rotated pipeline exists for the 64-row, pre-scaled fast form");
+template <int QR, bool FAST, bool PRE, int ROT = 0, class T = bf16_t>   // 16-row query tiles per wave: every K / V^T fragment read from LDS feeds QR MFMAs
+__global__ __launch_bounds__(256, 2) void attn_dit_kernel(AttnArgs a) {
+    static_assert(ROT == 0 || (QR == 4 && FAST && PRE), "the rotated pipeline exists for the 64-row, pre-scaled fast form");
     static_assert(!FAST || std::is_same<T, bf16_t>::value, "the fixed-reference and reference-free tiles rely on bf16's exponent range: fp16 takes the classical loop");
     typedef typename Vec8<T>::type T8;
     typedef typename Vec4<T>::type T4;
@@ -426,8 +424,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
     }
     // with a chunk mask the work per workgroup grows with its row index: dispatch the long ones first
     const int bx = a.chunk > 0 ? gridDim.x - 1 - bx0 : bx0;
-    constexpr int WG_ROWS = 16 * QR * NW;
-    constexpr int NLD = 8 / NW;            // 16-byte pieces of K (and of V^T) a thread moves per tile
+    constexpr int WG_ROWS = 64 * QR;
+    constexpr int NLD = 2;                 // 16-byte pieces of K (and of V^T) a thread moves per tile
     const int row0 = bx * WG_ROWS + wave * (16 * QR);
     const int kv_len = a.kv_len ? a.kv_len[b] : a.kv_len_const;
     const T* __restrict__ kb = reinterpret_cast<const T*>(a.k) + (long long)b * a.k_bs + (long long)h * a.k_hs;
@@ -598,49 +596,22 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
         bf16x8 kf[4][2], vf[4][2];
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
-            if constexpr (LAB & 4) {
-                kf[kt][0] = qf[kt % QR][0];
-                kf[kt][1] = qf[kt % QR][1];
-            } else {
-                kf[kt][0] = load8(&Ks[buf][(kt * 16 + fr) * LD + fg * 8]);
-                kf[kt][1] = load8(&Ks[buf][(kt * 16 + fr) * LD + 32 + fg * 8]);
-            }
+            kf[kt][0] = load8(&Ks[buf][(kt * 16 + fr) * LD + fg * 8]);
+            kf[kt][1] = load8(&Ks[buf][(kt * 16 + fr) * LD + 32 + fg * 8]);
         }
+        // (Measured and dropped, round 6: the de-paired order — the four first halves, then the four second halves, so that no two neighbouring MFMAs share an
+        // accumulator; bit-identical results, 1382 vs 958 us.)
         auto qk = [&](int i, f32x4 (&sv)[4]) {
-            if constexpr ((LAB & 128) != 0) {
-                // de-paired order: the four first halves, then the four second halves — no two neighbouring MFMAs share an accumulator (same sums, same order per accumulator)
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt) {
-                    if constexpr (PRE) sv[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][0], qf[i][0], nm_ref[i], 0, 0, 0);
-                    else sv[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][0], qf[i][0], f32x4{0, 0, 0, 0}, 0, 0, 0);
-                }
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt) mma32(sv[kt], kf[kt][1], qf[i][1]);
-                return;
-            }
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
                 // the accumulator starts at -m_ref (loop-invariant registers): the scores arrive shifted, exp2 is all that is left
-                if constexpr (LAB & 16) {
-                    sv[kt] = nm_ref[i] + f32x4{(float)key0, 1.0f, 2.0f, (float)kt};
-                } else {
-                    if constexpr (PRE) sv[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][0], qf[i][0], nm_ref[i], 0, 0, 0);
-                    else sv[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][0], qf[i][0], f32x4{0, 0, 0, 0}, 0, 0, 0);
-                    mma32(sv[kt], kf[kt][1], qf[i][1]);
-                }
+                if constexpr (PRE) sv[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][0], qf[i][0], nm_ref[i], 0, 0, 0);
+                else sv[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][0], qf[i][0], f32x4{0, 0, 0, 0}, 0, 0, 0);
+                mma32(sv[kt], kf[kt][1], qf[i][1]);
             }
         };
         auto sm = [&](int i, f32x4 (&sv)[4], bf16x8 (&pf)[2]) {
             if constexpr (TAIL) mask_tail(sv, key0, i);
-            if constexpr (LAB & 8) {                                      // (lab: the scores' raw bits as probabilities: no exp2, no conversion)
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    union { f32x4 f; bf16x8 b; } u;
-                    u.f = sv[2 * m] + sv[2 * m + 1];
-                    pf[m] = u.b;
-                }
-                return;
-            }
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -650,31 +621,14 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
                         pf[m][4 * hh + r] = f32_to_bf16(__builtin_amdgcn_exp2f(PRE ? sv[2 * m + hh][r] : __builtin_fmaf(sv[2 * m + hh][r], c, nm_ref[i][0])));   // -inf -> 0
         };
         auto pv = [&](int i, const bf16x8 (&pf)[2]) {
-            if constexpr ((LAB & 64) != 0) __builtin_amdgcn_s_setprio(1);
-            if constexpr (LAB & 16) {                                     // (lab: keep the probabilities alive without the matrix cores)
-                union { bf16x8 b; f32x4 f; } u0, u1;
-                u0.b = pf[0];
-                u1.b = pf[1];
-                o_acc[i][0] += u0.f;
-                o_acc[i][1] += u1.f;
-                return;
-            }
             f32x4 lt = {0, 0, 0, 0};
             mma32(lt, ones, pf[0]);
             mma32(lt, ones, pf[1]);
             l_acc[i] += lt[0];
-            if constexpr ((LAB & 128) != 0) {
 #pragma unroll
-                for (int m = 0; m < 2; ++m)
+            for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) mma32(o_acc[i][dt], vf[dt][m], pf[m]);
-            } else {
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) mma32(o_acc[i][dt], vf[dt][m], pf[m]);
-            }
-            if constexpr ((LAB & 64) != 0) __builtin_amdgcn_s_setprio(0);
+                for (int m = 0; m < 2; ++m) mma32(o_acc[i][dt], vf[dt][m], pf[m]);
         };
         // MFMA : VALU interleave of one pipeline step (masks: 0x8 MFMA, 0x2 VALU; the transcendental ops count as VALU)
         auto pin = [&](auto NM, auto NV) {
@@ -692,10 +646,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                if constexpr (LAB & 4) vf[dt][m] = qf[dt % QR][m];
-                else vf[dt][m] = load8(&Vs[buf][(dt * 16 + fr) * LD + m * 32 + fg * 8]);
-            }
+            for (int m = 0; m < 2; ++m) vf[dt][m] = load8(&Vs[buf][(dt * 16 + fr) * LD + m * 32 + fg * 8]);
         // (Measured and dropped: __builtin_amdgcn_sched_barrier(0) between the pipeline steps.  The disassembly then shows the pinned
         // "MFMA, exp x 3" interleave with hardly any s_nop left, but 30 more scratch instructions (spills inside the loop) and the kernel is
         // SLOWER: T = 5632 generic form 369 vs 337 us, flow solve (pre-scaled form) 564 vs 431 ms.)
@@ -723,12 +674,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
     const int n_full = lim_lo / KT;                                    // the first loop holds unmasked tiles only
     auto run = [&](auto&& tf) {
         for (int it = 0; it < n_full; ++it) {
-            const int buf = (LAB & 1) ? 0 : (it & 1), key0 = it * KT;
-            const bool more = (it + 1) < n_tiles && !(LAB & 1);
+            const int buf = it & 1, key0 = it * KT;
+            const bool more = (it + 1) < n_tiles;
             if (more) gload(key0 + KT);
             tf(buf, key0, std::false_type{});
             if (more) stash(buf ^ 1);
-            if constexpr (!(LAB & 2)) __syncthreads();
+            __syncthreads();
         }
         // masked tiles: one (the ragged end) without a chunk mask, the tiles between the first and the last row's chunk end with one
         for (int it = n_full; it < n_tiles; ++it) {
@@ -745,9 +696,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
         stash(0);
     }
     __syncthreads();
-    if constexpr ((LAB & 32) != 0) {                              // (lab: every other workgroup starts a fraction of a tile later)
-        if ((blockIdx.x + blockIdx.y + blockIdx.z) & 1) __builtin_amdgcn_s_sleep(24);
-    }
     bool classical = !FAST;
     if constexpr (FAST) {
         if (ROT == 0 && n_tiles > 0) {
@@ -907,7 +855,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
                 for (int r = 0; r < 4; ++r) bad |= ((__float_as_uint(o_acc[i][dt][r]) & 0x7f800000u) == 0x7f800000u);
         }
         classical = __syncthreads_or((int)bad) != 0;
-        if constexpr (LAB != 0) classical = false;
         if (classical) {
 #pragma unroll
             for (int i = 0; i < QR; ++i) {
@@ -940,724 +887,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_dit_kernel(Attn
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// DiT attention on the 32x32x16 MFMA shape (round 6).  Same contract, same operand layouts and the same fixed-reference softmax as attn_dit_kernel above, another
-// tile: v_mfma_f32_32x32x16_bf16 holds the matrix pipe 32 cycles per instruction (8 issue slots) instead of 16, so the exponentials of one score tile fit
-// in the shadow of the MFMAs of its neighbours, and half as many MFMA instructions compete for issue slots (MI355X guide: <= 5 fillers per 32x32x16 gap).
-//   S^T[key, q] = K Q^T   A = K rows (lane: key = l & 31, 8 consecutive d at 16 kk + 8 (l >> 5)), B = Q^T (lane: q = l & 31, the same d) — 4 MFMAs per 32 x 32 tile;
-//                         C/D: lane (q = l & 31, hi = l >> 5), register r: key (r & 3) + 8 (r >> 2) + 4 hi — a lane holds 16 scores of ONE query.
-//   O^T[d, q] += V^T P^T  the k-slot (hi, j) of a 16-key step is DEFINED as the key the lane already holds in registers 8 s + j of its score tile
-//                         (keys {0-3, 8-11} + 4 hi of the step): P^T needs no cross-lane move at all, and V^T goes into LDS with the two middle 4-key groups of
-//                         every 16 swapped, so that its fragment is one 16-byte read.  Row sums: fp32 adds per lane (the two lanes of a query meet once, at the end).
-// A wave owns QT query tiles of 32 rows (QT = 4: 128 rows, ONE wave per SIMD and the whole 512-register file, every K / V^T fragment read from LDS feeds 4 MFMAs;
-// QT = 2: two waves per SIMD).  Within a 64-key tile the work is cut into units of (32 keys) x (two query tiles) — 8 score MFMAs on two alternating accumulators,
-// 32 exponentials + 16 conversions, 8 PV MFMAs on four accumulators — and software-pipelined: scores of unit u+1 | softmax of unit u | PV of unit u-1.
-// Consecutive MFMAs never share an accumulator, so vector instructions may sit between any two of them (MI355X guide: an extra issue slot between two MFMAs on the
-// SAME accumulator costs 43 cycles; that is what the 16x16x32 tile's dependent pairs ran into).
-// ---------------------------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <int QT, bool PRE, int SUMS = 1, int PIN = 0, int WPS = 2, int PIPE = 1, int REF = 1>     // REF 0: no per-row reference — p = exp2(s) as it is; a workgroup whose rows leave [2^-60, 2^127] takes the classical loop; PIPE 0: units one after the other (the other waves of the SIMD cover a wave's vector phases); QT query tiles of 32 rows per wave; SUMS: row sums by fp32 adds (0) or on the matrix cores (1);
-                                                                         // PIN: vector instructions pinned behind every MFMA of a unit (0: the compiler's order); WPS: waves per SIMD the register budget is cut for
-__global__ __launch_bounds__(256, WPS) void attn_dit32_kernel(AttnArgs a) {
-    typedef bf16_t T;
-    constexpr int KT = 64, LD = 72;            // keys per tile; LDS row stride (144 B: the 16 rows of a ds_read_b128 lane group fall on 16 distinct 16-byte slots)
-    __shared__ __attribute__((aligned(16))) T Ks[2][KT * LD];
-    __shared__ __attribute__((aligned(16))) T Vs[2][64 * LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int fq = lane & 31, hi = lane >> 5;
-    int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
-    {   // XCD-aware order (see attn_dit_kernel): XCD e walks the row blocks of heads e, e + 8, ... one head after the other
-        const int nx = gridDim.x, nh = gridDim.y * gridDim.z;
-        if ((nh & 7) == 0) {
-            const int L = blockIdx.x + nx * (blockIdx.y + gridDim.y * blockIdx.z);
-            const int j = L >> 3, hb = (j / nx) * 8 + (L & 7);
-            bx = j % nx;
-            h = hb % gridDim.y;
-            b = hb / gridDim.y;
-        }
-    }
-    constexpr int WG_ROWS = 4 * QT * 32;
-    const int row0 = bx * WG_ROWS + wave * (QT * 32);
-    const int kv_len = a.kv_len ? a.kv_len[b] : a.kv_len_const;
-    const T* __restrict__ kb = reinterpret_cast<const T*>(a.k) + (long long)b * a.k_bs + (long long)h * a.k_hs;
-    const T* __restrict__ vb = reinterpret_cast<const T*>(a.vT) + (long long)b * a.v_bs + (long long)h * a.v_hs;
-
-    bf16x8 qf[QT][4];
-#pragma unroll
-    for (int i = 0; i < QT; ++i) {
-        const int r = row0 + i * 32 + fq;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-            qf[i][kk] = r < a.n_rows ? load8(reinterpret_cast<const T*>(a.q) + (long long)b * a.q_bs + (long long)h * a.q_hs + (long long)r * a.q_lo + kk * 16 + hi * 8) : zero8<T>();
-    }
-    // tile loader (the 4 waves together): thread t moves 2 x 16 B of K (rows t / 8 and t / 8 + 32, chunk t % 8) and 2 x 16 B of V^T
-    const int lrow = tid >> 3, lchunk = (tid & 7) * 8;
-    bf16x8 rk[2], rv[2];
-    auto gload = [&](int key0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            int key = key0 + lrow + i * 32;
-            key = key < kv_len ? key : kv_len - 1;                       // clamped rows are masked in the tail tile
-            rk[i] = load8(kb + (long long)key * 64 + lchunk);
-            rv[i] = load8(vb + (long long)(lrow + i * 32) * a.v_ld + key0 + lchunk);
-        }
-    };
-    // V^T in LDS: within every 16 keys the 4-key groups go in the order 0, 2, 1, 3 — the k-slots of a PV step as the score tile's registers define them
-    const int vc = tid & 7;                                              // the thread's 8-key chunk = groups 2 (vc & 1), 2 (vc & 1) + 1 of 16-key block vc / 2
-    const int vpos = (vc >> 1) * 16 + (vc & 1) * 4;
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            store8(&Ks[buf][(lrow + i * 32) * LD + lchunk], rk[i]);
-            bf16x4 lo, hv;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                lo[j] = rv[i][j];
-                hv[j] = rv[i][4 + j];
-            }
-            *reinterpret_cast<bf16x4*>(&Vs[buf][(lrow + i * 32) * LD + vpos]) = lo;
-            *reinterpret_cast<bf16x4*>(&Vs[buf][(lrow + i * 32) * LD + vpos + 8]) = hv;
-        }
-    };
-
-    f32x16 o_acc[QT][2];
-    float l_acc[QT];
-    auto zero16f = [] {                                                  // (a literal every time: a zero vector kept in registers across the key loop would cost 16 of them)
-        f32x16 z;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) z[r] = 0.0f;
-        return z;
-    };
-#define zero16 zero16f()
-#pragma unroll
-    for (int i = 0; i < QT; ++i) {
-        l_acc[i] = 0.0f;
-        o_acc[i][0] = zero16;
-        o_acc[i][1] = zero16;
-    }
-    const float c = PRE ? 1.0f : a.scale * 1.4426950408889634f;
-    f32x16 nm_ref[QT];                                                   // -m_ref of the lane's query in every register: the score accumulators start there
-
-    auto kfrag = [&](int buf, int kh, bf16x8 (&kf)[4]) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) kf[kk] = load8(&Ks[buf][(kh * 32 + fq) * LD + kk * 16 + hi * 8]);
-    };
-    auto vfrag = [&](int buf, int kh, bf16x8 (&vf)[2][2]) {
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) vf[dt][s] = load8(&Vs[buf][(dt * 32 + fq) * LD + (kh * 2 + s) * 16 + hi * 8]);
-    };
-    auto qk0 = [&](int i, const bf16x8 (&kf)[4], f32x16& s) {           // scores of one query tile against 32 keys, from zero
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[kk], qf[i][kk], kk == 0 ? zero16 : s, 0, 0, 0);
-    };
-    auto mask = [&](f32x16& s, int key0) {                               // keys at or beyond the sequence end (tail tile only)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            if (key0 + (r & 3) + 8 * (r >> 2) + 4 * hi >= kv_len) s[r] = -INFINITY;
-    };
-    auto pv1 = [&](int i, const bf16x8 (&vf)[2][2], const bf16x8 (&pf)[2]) {
-#pragma unroll
-        for (int st = 0; st < 4; ++st) o_acc[i][st & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[st & 1][st >> 1], pf[st >> 1], o_acc[i][st & 1], 0, 0, 0);
-    };
-
-    // ---- the fast tile: units of (32 keys) x (ONE query tile), pipelined  QK(u + 1) | SM(u) | PV(u - 1); the 4 dependent score MFMAs of unit u + 1 alternate with
-    //      the 4 PV MFMAs of unit u - 1 (two accumulators, twice each), so no two neighbours share an accumulator ----------------------------------------------
-    bf16x8 ones_sel;                                                     // A operand of the row-sum MFMA (16x16x32): row 0 sums the k-groups 0 and 2 (the two lanes of query n), row 1 the groups 1 and 3 (query n + 16)
-    {
-        const bool on = ((lane & 15) == 0 && ((lane >> 4) & 1) == 0) || ((lane & 15) == 1 && ((lane >> 4) & 1) == 1);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) ones_sel[e] = f32_to_bf16(on ? 1.0f : 0.0f);
-    }
-    f32x4 l_mm[QT];
-#pragma unroll
-    for (int i = 0; i < QT; ++i) l_mm[i] = f32x4{0, 0, 0, 0};
-    auto sm1 = [&](int i, f32x16& s, bf16x8 (&pf)[2], int key0, auto tail_tag) {
-        constexpr bool TAIL = decltype(tail_tag)::value;
-        if constexpr (TAIL) mask(s, key0);
-        float sum = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float e = __builtin_amdgcn_exp2f(PRE ? s[r] : (REF ? __builtin_fmaf(s[r], c, nm_ref[i][0]) : s[r] * c));      // -inf -> 0
-            if constexpr (SUMS == 0) sum += e;
-            pf[r >> 3][r & 7] = f32_to_bf16(e);
-        }
-        if constexpr (SUMS == 0) l_acc[i] += sum;
-    };
-    auto tile_fast = [&](int buf, int key0, auto tail_tag) {
-        constexpr int NU = 2 * QT;                                       // units: u = kh * QT + i
-        bf16x8 kf[4], vf[2][2];
-        f32x16 sa, sb;
-        bf16x8 pa[2], pb[2];
-        kfrag(buf, 0, kf);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[kk], qf[0][kk], kk == 0 ? ((PRE && REF) ? nm_ref[0] : zero16) : sa, 0, 0, 0);
-        vfrag(buf, 0, vf);
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int kh = u / QT, i = u % QT;
-            f32x16& s_cur = (u & 1) ? sb : sa;
-            f32x16& s_nxt = (u & 1) ? sa : sb;
-            bf16x8 (&p_cur)[2] = (u & 1) ? pb : pa;
-            bf16x8 (&p_prv)[2] = (u & 1) ? pa : pb;
-            const bool has_qk = u + 1 < NU, has_pv = u > 0;
-            const int in = (u + 1) % QT, ip = (u + QT - 1) % QT;         // query tiles of units u + 1 / u - 1
-            if (has_qk && in == 0) kfrag(buf, (u + 1) / QT, kf);         // the next 32 keys
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                if (has_qk) s_nxt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[st], qf[in][st], st == 0 ? ((PRE && REF) ? nm_ref[in] : zero16) : s_nxt, 0, 0, 0);
-                if (has_pv) o_acc[ip][st & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[st & 1][st >> 1], p_prv[st >> 1], o_acc[ip][st & 1], 0, 0, 0);
-            }
-            if (has_pv && i == 0 && kh == 1) vfrag(buf, 1, vf);          // unit u - 1 was the last of key half 0: its PV (just issued) was the last reader of that half's V^T fragments
-            sm1(i, s_cur, p_cur, key0 + kh * 32, tail_tag);
-            if constexpr (SUMS == 1) {
-                l_mm[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones_sel, p_cur[0], l_mm[i], 0, 0, 0);
-                l_mm[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones_sel, p_cur[1], l_mm[i], 0, 0, 0);
-            }
-            if constexpr (PIN > 0) {
-#pragma unroll
-                for (int g = 0; g < 8; ++g) {
-                    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x2, PIN, 0);
-                }
-            }
-            if constexpr (PIN < 0) __builtin_amdgcn_sched_barrier(0);    // units are scheduling regions: nothing moves across (keeps the fragments of later units out of the registers)
-        }
-        if (QT == 1) vfrag(buf, 1, vf);                                  // (QT = 1: unit 1 = key half 1 has no later slot that loads its fragments)
-        pv1(QT - 1, vf, ((NU - 1) & 1) ? pb : pa);                       // PV of the last unit
-    };
-    // ---- the same units one after the other (PIPE = 0): scores of all the wave's query tiles against 32 keys (independent accumulators alternate), their
-    //      probabilities, their PV — no second score / probability buffer, so three waves fit a SIMD at QT = 1 and cover each other's vector phases ------------------
-    auto tile_seq = [&](int buf, int key0, auto tail_tag) {
-#pragma unroll
-        for (int kh = 0; kh < 2; ++kh) {
-            bf16x8 kf[4], vf[2][2];
-            f32x16 s[QT];
-            bf16x8 pf[QT][2];
-            kfrag(buf, kh, kf);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int i = 0; i < QT; ++i) s[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[kk], qf[i][kk], kk == 0 ? ((PRE && REF) ? nm_ref[i] : zero16) : s[i], 0, 0, 0);
-            vfrag(buf, kh, vf);
-#pragma unroll
-            for (int i = 0; i < QT; ++i) sm1(i, s[i], pf[i], key0 + kh * 32, tail_tag);
-#pragma unroll
-            for (int st = 0; st < 4; ++st)
-#pragma unroll
-                for (int i = 0; i < QT; ++i) o_acc[i][st & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[st & 1][st >> 1], pf[i][st >> 1], o_acc[i][st & 1], 0, 0, 0);
-            if constexpr (SUMS == 1) {
-#pragma unroll
-                for (int i = 0; i < QT; ++i) {
-                    l_mm[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones_sel, pf[i][0], l_mm[i], 0, 0, 0);
-                    l_mm[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones_sel, pf[i][1], l_mm[i], 0, 0, 0);
-                }
-            }
-        }
-    };
-    // ---- classical online-softmax tile (the fall-back when a score outgrew its reference by 2^127), one query tile at a time ------------------------------
-    float m_run[QT];
-    auto tile_classical = [&](int buf, int key0, auto tail_tag) {
-        constexpr bool TAIL = decltype(tail_tag)::value;
-#pragma unroll
-        for (int i = 0; i < QT; ++i) {
-            bf16x8 kf[4], vf[2][2];
-            f32x16 s[2];                                                 // the two key halves
-            bf16x8 pf[2][2];
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh) {
-                kfrag(buf, kh, kf);
-                qk0(i, kf, s[kh]);
-                if constexpr (TAIL) mask(s[kh], key0 + kh * 32);
-            }
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmax2(mx, s[kh][r]);
-            mx = fmax2(mx, __shfl_xor(mx, 32, 64));                      // the two lanes of a query
-            const float m_new = fmax2(m_run[i], mx * c);
-            const float alpha = m_new == -INFINITY ? 1.0f : __builtin_amdgcn_exp2f(m_run[i] - m_new);      // exp2(-inf) == 0 on the first tile
-            float sum = 0.0f;
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float e = m_new == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(__builtin_fmaf(s[kh][r], c, -m_new));
-                    sum += e;
-                    pf[kh][r >> 3][r & 7] = f32_to_bf16(e);
-                }
-            l_acc[i] = l_acc[i] * alpha + sum;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o_acc[i][dt][r] *= alpha;
-            m_run[i] = m_new;
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh) {
-                vfrag(buf, kh, vf);
-                pv1(i, vf, pf[kh]);
-            }
-        }
-    };
-
-    const int n_tiles = (kv_len + KT - 1) / KT, n_full = kv_len / KT;
-    auto run = [&](auto&& tf) {
-        for (int it = 0; it < n_tiles; ++it) {
-            const int buf = it & 1, key0 = it * KT;
-            const bool more = (it + 1) < n_tiles;
-            if (more) gload(key0 + KT);
-            if (it < n_full) tf(buf, key0, std::false_type{});
-            else tf(buf, key0, std::true_type{});
-            if (more) stash(buf ^ 1);
-            __syncthreads();
-        }
-    };
-    if (n_tiles > 0) {
-        gload(0);
-        stash(0);
-    }
-    __syncthreads();
-    bool classical = false;
-    if (n_tiles > 0) {
-        // reference maximum of every row: its (masked) scores against the first key tile
-#pragma unroll
-        for (int i = 0; i < (REF ? QT : 0); ++i) {
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh) {
-                bf16x8 kf[4];
-                f32x16 s;
-                kfrag(0, kh, kf);
-                qk0(i, kf, s);
-                mask(s, kh * 32);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmax2(mx, s[r]);
-            }
-            float m = fmax2(mx, __shfl_xor(mx, 32, 64));
-            m = -fmax2(m * c, -1e30f);                                       // a row without a visible key in the tile: finite reference, p = 0
-#pragma unroll
-            for (int r = 0; r < 16; ++r) nm_ref[i][r] = m;
-            if constexpr (PRE) asm volatile("" : "+v"(nm_ref[i]));          // 16 REGISTERS from here on: the compiler must not rebuild the splat in front of every score tile
-        }
-        if constexpr (PIPE == 1) run(tile_fast);
-        else run(tile_seq);
-        if constexpr (SUMS == 1) {
-            // row sums off the matrix cores: query n < 16 in lane n, register 0; query n + 16 in lane n, register 1 (both lanes of a query already added)
-#pragma unroll
-            for (int i = 0; i < QT; ++i) {
-                const float v0 = __shfl(l_mm[i][0], lane & 15, 64), v1 = __shfl(l_mm[i][1], lane & 15, 64);
-                l_acc[i] = 0.5f * ((fq & 16) ? v1 : v0);                      // (halved: the epilogue adds the lane pair)
-            }
-        }
-        // overflow vote: any non-finite row sum / output sends the whole workgroup to the classical loop
-        unsigned bad = 0;
-#pragma unroll
-        for (int i = 0; i < QT; ++i) {
-            bad |= ((__float_as_uint(l_acc[i]) & 0x7f800000u) == 0x7f800000u);
-            if constexpr (!REF) {
-                const float lq = l_acc[i] + __shfl_xor(l_acc[i], 32, 64);
-                bad |= (row0 + i * 32 + fq < a.n_rows) && !(lq >= 8.7e-19f);            // a row whose probabilities sank below 2^-60: not enough range left
-            }
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) bad |= ((__float_as_uint(o_acc[i][dt][r]) & 0x7f800000u) == 0x7f800000u);
-        }
-        classical = __syncthreads_or((int)bad) != 0;
-        if (classical) {
-#pragma unroll
-            for (int i = 0; i < QT; ++i) {
-                l_acc[i] = 0.0f;
-                o_acc[i][0] = zero16;
-                o_acc[i][1] = zero16;
-            }
-#pragma unroll
-            for (int i = 0; i < QT; ++i) m_run[i] = -INFINITY;
-            gload(0);
-            stash(0);
-            __syncthreads();
-            run(tile_classical);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < QT; ++i) {
-        const float l = l_acc[i] + __shfl_xor(l_acc[i], 32, 64);             // the two lanes of a query hold the sums of complementary key sets
-        const int r = row0 + i * 32 + fq;
-        if (r >= a.n_rows) continue;
-        const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-        T* op = reinterpret_cast<T*>(a.out) + (long long)b * a.o_bs + (long long)h * a.o_hs + (long long)r * a.o_lo;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bf16x4 o4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o4[e] = f32_to_bf16(o_acc[i][dt][4 * g + e] * inv);
-                *reinterpret_cast<bf16x4*>(op + dt * 32 + 8 * g + 4 * hi) = o4;
-            }
-    }
-}
-#undef zero16
-
-#ifdef HVX_LAB      // (lab builds only: measured slower than the product tile, profiles/r06_attn_tile_ab.md; the hazards of its asm MFMAs are met by construction, not by the compiler)
-// ---------------------------------------------------------------------------------------------------------------------
-// DiT attention, ONE wave per SIMD with the whole 512-register file (round 6; the structure of the guide's fastest attention, at head_dim 64): a wave owns
-// FOUR query tiles of 32 rows (128 rows; 512 per workgroup), so every K / V^T fragment read from LDS feeds 4 MFMAs, and keeps O^T (128 registers) and Q (64)
-// in the ACCUMULATOR half of the file, where only MFMAs touch them; the scores start from 0
-// in VGPRs and the row's reference is ONE v_add per score on the way into the exponential (a 16-register start-value splat per query tile does not stay resident:
-// hipcc copies it into place in front of every use).  With a 512-register budget hipcc selects the AGPR-destination MFMA forms for its builtins and
-// copies every score out of the accumulator file (profiles/r06_attn_tile_ab.md), so the MFMAs here are inline asm with the register class of every operand spelled
-// out: O^T / row sums in AGPRs, scores and the K / V^T / P / Q fragments in VGPRs.  asm volatile statements keep their order; the compiler places the vector
-// instructions and the LDS reads between them and allocates the registers.  What the compiler does NOT do for an asm MFMA (cdna guide §5.7) is done by construction:
-//   * an MFMA result is read by a vector instruction only in the NEXT unit's region (sched_barrier between units), behind >= 2 further MFMAs (>= 64 cycles);
-//   * the P operand of a PV / row-sum MFMA was written by the vector ALU in the PREVIOUS region, a QK MFMA ahead of its first reader (no s_nop needed);
-//   * dependent MFMAs are either adjacent (accumulate chain: forwarded) or one independent MFMA (32 cycles) apart.
-// Same tile mathematics as attn_dit32_kernel (units of 32 keys x one query tile, QK(u + 1) | SM(u) | PV(u - 1), fixed-reference softmax, row sums on a selector MFMA).
-// ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void a4_qk_first0(f32x16& d, const bf16x8& k, const bf16x8& q) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(k), "v"(q));
-}
-__device__ __forceinline__ void a4_qk(f32x16& d, const bf16x8& k, const bf16x8& q) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(k), "v"(q));
-}
-__device__ __forceinline__ void a4_pv(f32x16& o, const bf16x8& v, const bf16x8& p) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(o) : "v"(v), "v"(p));
-}
-__device__ __forceinline__ void a4_sum(f32x4& l, const bf16x8& ones, const bf16x8& p) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(l) : "v"(ones), "v"(p));
-}
-
-template <bool PRE>
-__global__ __launch_bounds__(256, 1) void attn_dit_a4_kernel(AttnArgs a) {
-    typedef bf16_t T;
-    constexpr int QT = 4, KT = 64, LD = 72;
-    __shared__ __attribute__((aligned(16))) T Ks[2][KT * LD];
-    __shared__ __attribute__((aligned(16))) T Vs[2][64 * LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int fq = lane & 31, hi = lane >> 5;
-    int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
-    {   // XCD-aware order (see attn_dit_kernel)
-        const int nx = gridDim.x, nh = gridDim.y * gridDim.z;
-        if ((nh & 7) == 0) {
-            const int L = blockIdx.x + nx * (blockIdx.y + gridDim.y * blockIdx.z);
-            const int j = L >> 3, hb = (j / nx) * 8 + (L & 7);
-            bx = j % nx;
-            h = hb % gridDim.y;
-            b = hb / gridDim.y;
-        }
-    }
-    constexpr int WG_ROWS = 4 * QT * 32;
-    const int row0 = bx * WG_ROWS + wave * (QT * 32);
-    const int kv_len = a.kv_len ? a.kv_len[b] : a.kv_len_const;
-    const T* __restrict__ kb = reinterpret_cast<const T*>(a.k) + (long long)b * a.k_bs + (long long)h * a.k_hs;
-    const T* __restrict__ vb = reinterpret_cast<const T*>(a.vT) + (long long)b * a.v_bs + (long long)h * a.v_hs;
-
-    bf16x8 qf[QT][4];
-#pragma unroll
-    for (int i = 0; i < QT; ++i) {
-        const int r = row0 + i * 32 + fq;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-            qf[i][kk] = r < a.n_rows ? load8(reinterpret_cast<const T*>(a.q) + (long long)b * a.q_bs + (long long)h * a.q_hs + (long long)r * a.q_lo + kk * 16 + hi * 8) : zero8<T>();
-    }
-    const int lrow = tid >> 3, lchunk = (tid & 7) * 8;
-    bf16x8 rk[2], rv[2];
-    auto gload = [&](int key0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            int key = key0 + lrow + i * 32;
-            key = key < kv_len ? key : kv_len - 1;
-            rk[i] = load8(kb + (long long)key * 64 + lchunk);
-            rv[i] = load8(vb + (long long)(lrow + i * 32) * a.v_ld + key0 + lchunk);
-        }
-    };
-    const int vc = tid & 7;
-    const int vpos = (vc >> 1) * 16 + (vc & 1) * 4;
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            store8(&Ks[buf][(lrow + i * 32) * LD + lchunk], rk[i]);
-            bf16x4 lo, hv;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                lo[j] = rv[i][j];
-                hv[j] = rv[i][4 + j];
-            }
-            *reinterpret_cast<bf16x4*>(&Vs[buf][(lrow + i * 32) * LD + vpos]) = lo;
-            *reinterpret_cast<bf16x4*>(&Vs[buf][(lrow + i * 32) * LD + vpos + 8]) = hv;
-        }
-    };
-    auto zero16f = [] {
-        f32x16 z;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) z[r] = 0.0f;
-        return z;
-    };
-    f32x16 o_acc[QT][2];
-    f32x4 l_mm[QT];
-#pragma unroll
-    for (int i = 0; i < QT; ++i) {
-        o_acc[i][0] = zero16f();
-        o_acc[i][1] = zero16f();
-        l_mm[i] = f32x4{0, 0, 0, 0};
-    }
-    const float c = PRE ? 1.0f : a.scale * 1.4426950408889634f;
-    float nm_ref[QT];                                                    // -m_ref of the lane's query: one register per query tile, subtracted on the way into the exponential
-    bf16x8 ones_sel;
-    {
-        const bool on = ((lane & 15) == 0 && ((lane >> 4) & 1) == 0) || ((lane & 15) == 1 && ((lane >> 4) & 1) == 1);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) ones_sel[e] = f32_to_bf16(on ? 1.0f : 0.0f);
-    }
-    auto kfrag = [&](int buf, int kh, bf16x8 (&kf)[4]) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) kf[kk] = load8(&Ks[buf][(kh * 32 + fq) * LD + kk * 16 + hi * 8]);
-    };
-    auto vfrag = [&](int buf, int kh, bf16x8 (&vf)[2][2]) {
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) vf[dt][s] = load8(&Vs[buf][(dt * 32 + fq) * LD + (kh * 2 + s) * 16 + hi * 8]);
-    };
-    auto mask = [&](f32x16& s, int key0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            if (key0 + (r & 3) + 8 * (r >> 2) + 4 * hi >= kv_len) s[r] = -INFINITY;
-    };
-    // four scores of a unit -> probabilities (slice q = registers 4 q .. 4 q + 3 of the score tile): the vector work is cut into slices so that it can be PINNED between
-    // the MFMAs.  The compiler sees an asm MFMA as an instruction that takes no time and gathers all vector work in front of the MFMA run (nothing overlaps: 1137 us, and
-    // the first slice then reads scores its MFMA has not finished: wrong results); slices pinned behind PAIRS of MFMAs: 1103 us (this form); one 5-instruction slice behind
-    // EVERY MFMA — which puts vector instructions between MFMAs on the same accumulator: 2990 us (the guide's 43-cycle cliff, three times per unit).
-    auto sm_slice = [&](int i, int q, f32x16& s, bf16x8 (&pf)[2], int key0, auto tail_tag) {
-        constexpr bool TAIL = decltype(tail_tag)::value;
-#pragma unroll
-        for (int r = 4 * q; r < 4 * q + 4; ++r) {
-            float x = s[r];
-            if constexpr (TAIL)
-                if (key0 + (r & 3) + 8 * (r >> 2) + 4 * hi >= kv_len) x = -INFINITY;
-            const float e = __builtin_amdgcn_exp2f(PRE ? x + nm_ref[i] : __builtin_fmaf(x, c, nm_ref[i]));
-            pf[r >> 3][r & 7] = f32_to_bf16(e);
-        }
-    };
-    // one 64-key tile: 8 units u = kh * 4 + i.  Region of unit u:  Q0 P0 Q1 P1 | slice 0 | Q2 P2 | slice 1 | Q3 P3 | slice 2 | sum sum | slice 3   (Q = score MFMA of unit
-    // u + 1, P = PV MFMA of unit u - 1, slices = softmax of unit u; every `|` is a sched_barrier).  The first slice sits behind >= 2 MFMAs: the scores it reads were
-    // finished by the previous region's Q3 (>= 12 wait states ago in every case, the tile's first region included).
-    auto tile_fast = [&](int buf, int key0, auto tail_tag) {
-        constexpr int NU = 2 * QT;
-        bf16x8 kf[4], vf[2][2];
-        f32x16 sa, sb;
-        bf16x8 pa[2], pb[2];
-        kfrag(buf, 0, kf);
-        vfrag(buf, 0, vf);
-        a4_qk_first0(sa, kf[0], qf[0][0]);
-#pragma unroll
-        for (int kk = 1; kk < 4; ++kk) a4_qk(sa, kf[kk], qf[0][kk]);
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            __builtin_amdgcn_sched_barrier(0);
-            const int kh = u / QT, i = u % QT;
-            f32x16& s_cur = (u & 1) ? sb : sa;
-            f32x16& s_nxt = (u & 1) ? sa : sb;
-            bf16x8 (&p_cur)[2] = (u & 1) ? pb : pa;
-            bf16x8 (&p_prv)[2] = (u & 1) ? pa : pb;
-            const bool has_qk = u + 1 < NU, has_pv = u > 0;
-            const int in = (u + 1) % QT, ip = (u + QT - 1) % QT;
-            if (has_qk && in == 0) kfrag(buf, (u + 1) / QT, kf);
-            auto pair = [&](int st) __attribute__((always_inline)) {
-                if (has_qk) {
-                    if (st == 0) a4_qk_first0(s_nxt, kf[0], qf[in][0]);
-                    else a4_qk(s_nxt, kf[st], qf[in][st]);
-                }
-                if (has_pv) a4_pv(o_acc[ip][st & 1], vf[st & 1][st >> 1], p_prv[st >> 1]);
-            };
-            pair(0);
-            pair(1);
-            __builtin_amdgcn_sched_barrier(0);
-            sm_slice(i, 0, s_cur, p_cur, key0 + kh * 32, tail_tag);
-            __builtin_amdgcn_sched_barrier(0);
-            pair(2);
-            __builtin_amdgcn_sched_barrier(0);
-            sm_slice(i, 1, s_cur, p_cur, key0 + kh * 32, tail_tag);
-            __builtin_amdgcn_sched_barrier(0);
-            pair(3);
-            __builtin_amdgcn_sched_barrier(0);
-            sm_slice(i, 2, s_cur, p_cur, key0 + kh * 32, tail_tag);
-            __builtin_amdgcn_sched_barrier(0);
-            if (has_pv) {
-                a4_sum(l_mm[ip], ones_sel, p_prv[0]);
-                a4_sum(l_mm[ip], ones_sel, p_prv[1]);
-            }
-            if (has_pv && i == 0 && kh == 1) vfrag(buf, 1, vf);
-            __builtin_amdgcn_sched_barrier(0);
-            sm_slice(i, 3, s_cur, p_cur, key0 + kh * 32, tail_tag);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        {
-            bf16x8 (&p_lst)[2] = ((NU - 1) & 1) ? pb : pa;
-#pragma unroll
-            for (int st = 0; st < 4; ++st) a4_pv(o_acc[QT - 1][st & 1], vf[st & 1][st >> 1], p_lst[st >> 1]);
-            a4_sum(l_mm[QT - 1], ones_sel, p_lst[0]);
-            a4_sum(l_mm[QT - 1], ones_sel, p_lst[1]);
-        }
-    };
-    // classical online-softmax tile (fall-back), one query tile at a time; the compiler moves O^T between the register halves for the rescale
-    float m_run[QT], l_acc[QT];
-    auto tile_classical = [&](int buf, int key0, auto tail_tag) {
-        constexpr bool TAIL = decltype(tail_tag)::value;
-#pragma unroll
-        for (int i = 0; i < QT; ++i) {
-            bf16x8 kf[4], vf[2][2];
-            f32x16 s[2];
-            bf16x8 pf[2][2];
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh) {
-                kfrag(buf, kh, kf);
-                a4_qk_first0(s[kh], kf[0], qf[i][0]);
-#pragma unroll
-                for (int kk = 1; kk < 4; ++kk) a4_qk(s[kh], kf[kk], qf[i][kk]);
-            }
-            asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");             // the last chain's result: 16 states before the vector ALU reads it
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (TAIL) {
-                mask(s[0], key0);
-                mask(s[1], key0 + 32);
-            }
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmax2(mx, s[kh][r]);
-            mx = fmax2(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmax2(m_run[i], mx * c);
-            const float alpha = m_new == -INFINITY ? 1.0f : __builtin_amdgcn_exp2f(m_run[i] - m_new);
-            float sum = 0.0f;
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float e = m_new == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(__builtin_fmaf(s[kh][r], c, -m_new));
-                    sum += e;
-                    pf[kh][r >> 3][r & 7] = f32_to_bf16(e);
-                }
-            l_acc[i] = l_acc[i] * alpha + sum;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o_acc[i][dt][r] *= alpha;
-            m_run[i] = m_new;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh) {
-                vfrag(buf, kh, vf);
-#pragma unroll
-                for (int st = 0; st < 4; ++st) a4_pv(o_acc[i][st & 1], vf[st & 1][st >> 1], pf[kh][st >> 1]);
-            }
-            asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    const int n_tiles = (kv_len + KT - 1) / KT, n_full = kv_len / KT;
-    auto run = [&](auto&& tf) {
-        for (int it = 0; it < n_full; ++it) {                             // (two loops, not one with a branch: the register assignment of O^T then never has to be shuffled between two loop bodies)
-            const int buf = it & 1, key0 = it * KT;
-            const bool more = (it + 1) < n_tiles;
-            if (more) gload(key0 + KT);
-            tf(buf, key0, std::false_type{});
-            if (more) stash(buf ^ 1);
-            __syncthreads();
-        }
-        for (int it = n_full; it < n_tiles; ++it) {                       // the ragged last tile
-            const int buf = it & 1, key0 = it * KT;
-            tf(buf, key0, std::true_type{});
-            __syncthreads();
-        }
-    };
-    if (n_tiles > 0) {
-        gload(0);
-        stash(0);
-    }
-    __syncthreads();
-    bool classical = false;
-    if (n_tiles > 0) {
-#pragma unroll
-        for (int i = 0; i < QT; ++i) {
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh) {
-                bf16x8 kf[4];
-                f32x16 s;
-                kfrag(0, kh, kf);
-                a4_qk_first0(s, kf[0], qf[i][0]);
-#pragma unroll
-                for (int kk = 1; kk < 4; ++kk) a4_qk(s, kf[kk], qf[i][kk]);
-                asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                mask(s, kh * 32);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmax2(mx, s[r]);
-            }
-            float m = fmax2(mx, __shfl_xor(mx, 32, 64));
-            m = -fmax2(m * c, -1e30f);
-            nm_ref[i] = m;
-        }
-        run(tile_fast);
-        asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");                 // the last MFMAs' results before anything reads O^T / the row sums
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < QT; ++i) {
-            const float v0 = __shfl(l_mm[i][0], lane & 15, 64), v1 = __shfl(l_mm[i][1], lane & 15, 64);
-            l_acc[i] = 0.5f * ((fq & 16) ? v1 : v0);
-        }
-        unsigned bad = 0;
-#pragma unroll
-        for (int i = 0; i < QT; ++i) {
-            bad |= ((__float_as_uint(l_acc[i]) & 0x7f800000u) == 0x7f800000u);
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) bad |= ((__float_as_uint(o_acc[i][dt][r]) & 0x7f800000u) == 0x7f800000u);
-        }
-        classical = __syncthreads_or((int)bad) != 0;
-        if (classical) {
-#pragma unroll
-            for (int i = 0; i < QT; ++i) {
-                l_acc[i] = 0.0f;
-                m_run[i] = -INFINITY;
-                o_acc[i][0] = zero16f();
-                o_acc[i][1] = zero16f();
-            }
-            gload(0);
-            stash(0);
-            __syncthreads();
-            run(tile_classical);
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < QT; ++i) l_acc[i] = 0.0f;
-    }
-#pragma unroll
-    for (int i = 0; i < QT; ++i) {
-        const float l = l_acc[i] + __shfl_xor(l_acc[i], 32, 64);
-        const int r = row0 + i * 32 + fq;
-        if (r >= a.n_rows) continue;
-        const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-        T* op = reinterpret_cast<T*>(a.out) + (long long)b * a.o_bs + (long long)h * a.o_hs + (long long)r * a.o_lo;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bf16x4 o4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o4[e] = f32_to_bf16(o_acc[i][dt][4 * g + e] * inv);
-                *reinterpret_cast<bf16x4*>(op + dt * 32 + 8 * g + 4 * hi) = o4;
-            }
-    }
-}
-#endif  // HVX_LAB
-
 template <class T>
 static int launch_t(const AttnArgs& a_in, hipStream_t s) {
     AttnArgs a = a_in;
@@ -1675,57 +904,11 @@ static int launch_t(const AttnArgs& a_in, hipStream_t s) {
         // T = 5632, 704 workgroups: 364 vs 337 us; 2816 workgroups: flow solve 441 vs 431 ms.  The rounds are not uniform enough for the
         // tail to be worth a kernel boundary.)
         const dim3 g4((a.n_rows + 255) / 256, a.heads, a.batch), g2((a.n_rows + 127) / 128, a.heads, a.batch);
-#ifdef HVX_LAB
-        // (NW = 8, measured on MI355X round 5: 1158 vs 1055 us at B = 8, 349 vs 275 us at B = 2 — the barrier over eight waves costs more than the halved
-        // staging saves; two independent 4-wave workgroups per CU drift apart and cover each other.  Lab builds only.)
-        const int nw8 = opt(OPT_ATTN_NW) == 8;
-        if (nw8 && a.n_rows >= 2048 && a.chunk <= 0 && a.q_log2) {
-            const dim3 g8((a.n_rows + 511) / 512, a.heads, a.batch);
-            hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 0, 8>), g8, dim3(512), 0, s, a);
-            prof_end(slot, s);
-            return hipGetLastError() == hipSuccess ? 0 : (set_error("attention launch failed"), -1);
-        }
-        const int lab = (int)opt(OPT_ATTN_LAB);
-        if (lab && a.n_rows >= 2048 && a.chunk <= 0 && a.q_log2) {
-            switch (lab) {
-                case 1: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 1>), g4, dim3(256), 0, s, a); break;
-                case 2: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 2>), g4, dim3(256), 0, s, a); break;
-                case 3: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 3>), g4, dim3(256), 0, s, a); break;
-                case 7: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 7>), g4, dim3(256), 0, s, a); break;
-                case 11: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 11>), g4, dim3(256), 0, s, a); break;
-                case 15: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 15>), g4, dim3(256), 0, s, a); break;
-                case 19: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 19>), g4, dim3(256), 0, s, a); break;
-                case 23: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 23>), g4, dim3(256), 0, s, a); break;
-                case 32: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 32>), g4, dim3(256), 0, s, a); break;
-                case 64: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 64>), g4, dim3(256), 0, s, a); break;
-                case 96: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 96>), g4, dim3(256), 0, s, a); break;
-                case 128: hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 128>), g4, dim3(256), 0, s, a); break;     // de-paired MFMA order (bit-identical results; round 6: 1382 vs 958 us)
-                default: return set_error("option attn_lab=%d is not instantiated", lab), -1;
-            }
-            prof_end(slot, s);
-            return hipGetLastError() == hipSuccess ? 0 : (set_error("attention launch failed"), -1);
-        }
-#endif
-        // attn_dit_form: 0 = per shape (below), 16 = the 16x16x32 tile whatever the shape says, 32 = the 32x32x16 tile (attn_dit32_kernel: measured SLOWER on MI355X,
-        // profiles/r06_attn_tile_ab.md — kept selectable, parity-tested, not the default)
+        // attn_dit_form: 0 = per shape and 17 = the same, said explicitly: the rotated pipeline (ROT 1) where it exists — pre-scaled queries, no chunk mask, >= 2048 rows: the
+        // DiT of the batched path — and the in-tile pipeline elsewhere; 16 = the in-tile pipeline everywhere (the round-5 product tile)
         const int form = (int)opt(OPT_ATTN_DIT_FORM);
-#ifdef HVX_LAB
-        if (form == 48 && a.chunk <= 0) {                               // (lab: the one-wave-per-SIMD, 512-register form with asm MFMAs)
-            const dim3 g4q((a.n_rows + 511) / 512, a.heads, a.batch);
-            if (a.q_log2) hipLaunchKernelGGL((attn_dit_a4_kernel<true>), g4q, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((attn_dit_a4_kernel<false>), g4q, dim3(256), 0, s, a);
-            prof_end(slot, s);
-            return hipGetLastError() == hipSuccess ? 0 : (set_error("attention launch failed"), -1);
-        }
-#endif
-        // 0 / 17: the rotated pipeline (ROT 1) where it exists — pre-scaled queries, no chunk mask, >= 2048 rows: the DiT of the batched path —; 16: the in-tile
-        // pipeline everywhere (the round-5 product tile)
         if ((form == 0 || form == 17) && a.chunk <= 0 && a.n_rows >= 2048 && a.q_log2) {
-            hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 0, 4, 1>), g4, dim3(256), 0, s, a);
-        } else if (form == 32 && a.chunk <= 0) {
-            const dim3 g1q((a.n_rows + 127) / 128, a.heads, a.batch);
-            if (a.q_log2) hipLaunchKernelGGL((attn_dit32_kernel<1, true>), g1q, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((attn_dit32_kernel<1, false>), g1q, dim3(256), 0, s, a);
+            hipLaunchKernelGGL((attn_dit_kernel<4, true, true, 1>), g4, dim3(256), 0, s, a);
         } else if (a.n_rows >= 2048 && a.chunk <= 0) {
             if (a.q_log2) hipLaunchKernelGGL((attn_dit_kernel<4, true, true>), g4, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((attn_dit_kernel<4, true, false>), g4, dim3(256), 0, s, a);
@@ -1775,12 +958,12 @@ static int launch_dit_f16(const AttnArgs& a, hipStream_t s) {
     // 64 query rows per wave on long unmasked sequences, 32 otherwise (the bf16 tile's choice, same reasons)
     if (a.n_rows >= 2048 && a.chunk <= 0) {
         const dim3 g4((a.n_rows + 255) / 256, a.heads, a.batch);
-        if (a.q_log2) hipLaunchKernelGGL((attn_dit_kernel<4, false, true, 0, 4, 0, f16_t>), g4, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((attn_dit_kernel<4, false, false, 0, 4, 0, f16_t>), g4, dim3(256), 0, s, a);
+        if (a.q_log2) hipLaunchKernelGGL((attn_dit_kernel<4, false, true, 0, f16_t>), g4, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((attn_dit_kernel<4, false, false, 0, f16_t>), g4, dim3(256), 0, s, a);
     } else {
         const dim3 g2((a.n_rows + 127) / 128, a.heads, a.batch);
-        if (a.q_log2) hipLaunchKernelGGL((attn_dit_kernel<2, false, true, 0, 4, 0, f16_t>), g2, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((attn_dit_kernel<2, false, false, 0, 4, 0, f16_t>), g2, dim3(256), 0, s, a);
+        if (a.q_log2) hipLaunchKernelGGL((attn_dit_kernel<2, false, true, 0, f16_t>), g2, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((attn_dit_kernel<2, false, false, 0, f16_t>), g2, dim3(256), 0, s, a);
     }
     prof_end(slot, s);
     return hipGetLastError() == hipSuccess ? 0 : (set_error("attention launch failed"), -1);

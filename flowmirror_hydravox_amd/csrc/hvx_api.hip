@@ -62,7 +62,6 @@ const OptDef g_opt_defs[OPT_COUNT] = {
     {"conv_resident", 1, 0}, {"conv64_resident", 1, 0}, {"x3p8", 1, 0}, {"attn_dit_form", 0, 0}, {"dec_fuse_rows", 0, 0},
     {"dec_gpw_qkv", 1, 0}, {"dec_gpw_res", 1, 0}, {"dec_gpw_mlp", 3, 0}, {"dec_gpw_down", 2, 0}, {"dec_gpw_out", 3, 0}, {"dec_gpw_hmlp", 11, 0},
     {"gemm_big_mfma", 16, 1}, {"head_down_split", 0, 1},
-    {"attn_lab", 0, 1}, {"attn_nw", 4, 1},
 };
 static std::atomic<long long> g_opt_val[OPT_COUNT];
 static std::atomic<bool> g_opt_init{false};
@@ -119,12 +118,8 @@ int hvx_set_option(const char* key, int64_t value) {
     if ((i == OPT_X3P8 || i == OPT_CONV_RESIDENT || i == OPT_CONV64_RESIDENT) && value != 0 && value != 1) return set_error("hvx_set_option: %s must be 0 or 1, got %lld", key, (long long)value), -1;
     if (i >= OPT_DEC_GPW_QKV && i <= OPT_DEC_GPW_HMLP && (value < 1 || value > 64)) return set_error("hvx_set_option: %s must be 1..64, got %lld", key, (long long)value), -1;
     if (i == OPT_ATT_WAVES && value != 4 && value != 8) return set_error("hvx_set_option: att_waves must be 4 or 8, got %lld", (long long)value), -1;
-    #ifdef HVX_LAB
-    const bool form_ok = value == 0 || value == 16 || value == 17 || value == 32 || value == 48;
-#else
-    const bool form_ok = value == 0 || value == 16 || value == 17 || value == 32;
-#endif
-    if (i == OPT_ATTN_DIT_FORM && !form_ok) return set_error("hvx_set_option: attn_dit_form must be 0, 16, 17 or 32 (48: lab builds only), got %lld", (long long)value), -1;
+    const bool form_ok = value == 0 || value == 16 || value == 17;
+    if (i == OPT_ATTN_DIT_FORM && !form_ok) return set_error("hvx_set_option: attn_dit_form must be 0, 16 or 17, got %lld", (long long)value), -1;
     opt_init();
     g_opt_val[i].store(value, std::memory_order_relaxed);
     return 0;

@@ -6,7 +6,7 @@
 // Values are read at dispatch time (an atomic load per launch decision); a captured step graph keeps the forms it was captured with.
 #pragma once
 
-#if (defined(HVX_LAB_GEMM_EPI) || defined(HVX_LAB_X3_EPI) || defined(HVX_ATTN_LAB)) && !defined(HVX_LAB)
+#if (defined(HVX_LAB_GEMM_EPI) || defined(HVX_LAB_X3_EPI)) && !defined(HVX_LAB)
 #error "timing-only kernel variants (results are not stored) need -DHVX_LAB: the loader then refuses the library unless HVX_LIB_PATH names it"
 #endif
 
@@ -24,7 +24,7 @@ enum OptId : int {
     OPT_CONV64_RESIDENT,       // 1: the vocoder's 64-channel split-bf16 convolutions in the resident-row form; 0: tiled (the tests compare the two)
     OPT_X3P8,                  // 1: the 8-wave 128 x 128 x 64 tile for the vocoder's 128- / 256-channel split-bf16 convolutions; 0: the 4-wave tile
     OPT_ATTN_DIT_FORM,         // DiT attention tile: 0 = chosen per shape (16x16x32 MFMAs; the pipeline rotated across key tiles where that form exists), 17 = the same,
-                               // 16 = the in-tile pipeline everywhere (the round-5 tile), 32 = the 32x32x16 tile (measured slower, kept selectable)
+                               // 16 = the in-tile pipeline everywhere (the round-5 tile)
     OPT_DEC_FUSE_ROWS,         // decode grids of up to this many rows build the o_proj's activation fragments from the attention's key-split partials (no combine launch);
                                // 0 = never (the default: bit-identical and measured 12 % SLOWER per step, profiles/r06_decode_fuse_ab.log — kept selectable for that A / B)
     // column groups per workgroup of the decode GEMM launches (gemm_dec.hip), 1..64; the defaults are the tuned values.  A launch geometry only: every
@@ -34,8 +34,6 @@ enum OptId : int {
     // ---- lab (settable with -DHVX_LAB only) ----
     OPT_GEMM_BIG_MFMA,         // MFMA shape of the 256-tile Linear's K-loop: 16 (16x16x32) or 32 (32x32x16: bit-identical, measured 4 % slower)
     OPT_HEAD_DOWN_SPLIT,       // forced K split of the MTP heads' down projection; 0 = chosen per grid
-    OPT_ATTN_LAB,              // timing-only variants of the DiT attention loop (results are garbage): bit mask, see attention.hip
-    OPT_ATTN_NW,               // 8: one 8-wave workgroup per CU for the DiT attention (lab)
     OPT_COUNT
 };
 

@@ -916,9 +916,9 @@ def test_library_options_are_one_switchboard_and_lab_ones_are_refused():
     lib = _lib.load()
     assert int(lib.hvx_is_lab_build()) == 0 and lib.hvx_build_flags() == b''
     opts = _lib.options()
-    assert {'dec_gemm', 'conv64_resident', 'x3p8', 'att_chunk', 'att_waves', 'gemm_big_gw', 'attn_lab'} <= set(opts)
+    assert {'dec_gemm', 'conv64_resident', 'x3p8', 'att_chunk', 'att_waves', 'gemm_big_gw', 'head_down_split'} <= set(opts)
     assert all(v == d for v, d, _ in opts.values())                       # nothing has been switched in this process
-    assert opts['attn_lab'][2] and not opts['dec_gemm'][2]
+    assert opts['head_down_split'][2] and not opts['dec_gemm'][2]
     with _lib.option_scope(dec_gemm=0, att_chunk=512):
         assert _lib.get_option('dec_gemm') == 0 and _lib.get_option('att_chunk') == 512
     assert _lib.get_option('dec_gemm') == 1 and _lib.get_option('att_chunk') == 0
@@ -929,8 +929,9 @@ def test_library_options_are_one_switchboard_and_lab_ones_are_refused():
     with _lib.option_scope(dec_gpw_qkv=3, dec_gpw_hmlp=2):                # the decode GEMMs' launch geometry: tests/test_gpu_decode_gemm.py moves the grid's edges with it
         assert _lib.get_option('dec_gpw_qkv') == 3 and _lib.get_option('dec_gpw_hmlp') == 2
     assert _lib.get_option('dec_gpw_qkv') == 1 and _lib.get_option('dec_gpw_hmlp') == 11
-    for key, val, msg in (('no_such_option', 1, 'unknown option'), ('att_chunk', 100, 'multiple of 128'), ('att_waves', 5, '4 or 8'), ('attn_lab', 3, 'lab option'),
-                          ('attn_dit_form', 18, '0, 16, 17 or 32'), ('attn_dit_form', 48, 'lab builds only'), ('dec_fuse_rows', 300, '0..256'), ('dec_gpw_qkv', 0, '1..64'), ('dec_gpw_down', 65, '1..64'),
+    for key, val, msg in (('no_such_option', 1, 'unknown option'), ('att_chunk', 100, 'multiple of 128'), ('att_waves', 5, '4 or 8'), ('head_down_split', 3, 'lab option'),
+                          ('attn_dit_form', 18, '0, 16 or 17'), ('attn_dit_form', 32, '0, 16 or 17'), ('attn_dit_form', 48, '0, 16 or 17'),
+                          ('attn_lab', 1, 'unknown option'), ('attn_nw', 8, 'unknown option'), ('dec_fuse_rows', 300, '0..256'), ('dec_gpw_qkv', 0, '1..64'), ('dec_gpw_down', 65, '1..64'),
                           ('x3p8', 2, 'x3p8 must be 0 or 1'), ('conv64_resident', -1, 'conv64_resident must be 0 or 1'), ('conv_resident', 8, 'conv_resident must be 0 or 1')):
         with pytest.raises(_lib.HvxError, match=msg):
             _lib.set_option(key, val)

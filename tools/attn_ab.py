@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """A / B of the DiT attention tiles at the bench shape, in ONE process, interleaved rounds (cdna guide §5.4 rule 24):
 
-    python tools/attn_ab.py [--forms 16,32,33] [--batch 8] [--t 5632] [--rounds 5]
+    python tools/attn_ab.py [--forms 16,17] [--batch 8] [--t 5632] [--rounds 5]
 
-Every form (option attn_dit_form: 16 = the 16x16x32 tile with the in-tile pipeline, 17 = with the pipeline rotated across key tiles (the default), 32 = the 32x32x16 tile, csrc/attention.hip) is first checked against an fp32 torch
+Every form (option attn_dit_form: 16 = the 16x16x32 tile with the in-tile pipeline, 17 = with the pipeline rotated across key tiles (the default), csrc/attention.hip) is first checked against an fp32 torch
 reference on one (batch, head) and against the 16x16x32 form on everything, then timed: median and minimum of `rounds` interleaved rounds of `iters` launches."""
 import argparse
 import os
@@ -17,7 +17,7 @@ from flowmirror_hydravox_amd import _lib, ops  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--forms', default='16,32')
+    ap.add_argument('--forms', default='16,17')
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--t', type=int, default=5632)
     ap.add_argument('--rounds', type=int, default=5)
