@@ -71,6 +71,13 @@ class AttnArgs(C.Structure):
                 ('n_splits', c_i32), ('split_chunk', c_i32), ('part_o', c_vp), ('part_ml', c_vp), ('chunk', c_i32), ('q_log2', c_i32)]
 
 
+class AttnWindowArgs(C.Structure):
+    _fields_ = [('dtype', c_i32), ('batch', c_i32), ('heads', c_i32), ('rows', c_i32), ('q_pad', c_i32),
+                ('q', c_vp), ('out', c_vp), ('k', c_vp), ('vT', c_vp), ('cap', c_i32), ('slot_stride', c_i64),
+                ('kv_slot', c_vp), ('r0', c_vp), ('kv_len', c_vp), ('r0_const', c_i32), ('kv_max', c_i32), ('chunk', c_i32),
+                ('scale', c_f32), ('q_log2', c_i32), ('split_chunk', c_i32), ('max_splits', c_i32), ('part_o', c_vp), ('part_ml', c_vp)]
+
+
 class LlmAttnArgs(C.Structure):
     _fields_ = [('dtype', c_i32), ('batch', c_i32), ('heads', c_i32), ('n_rows', c_i32), ('kn', c_i32),
                 ('q', c_vp), ('q_bs', c_i64), ('q_hs', c_i64), ('q_hi', c_i64), ('q_lo', c_i64),
@@ -223,6 +230,19 @@ SYMBOLS = {
     'hvx_cfm_solve_stream_batch': (c_i32, [c_vp, c_vp, c_vp, c_sz, c_i32, c_i32, C.POINTER(c_i32), c_vp, c_vp, c_vp, c_vp, c_i32, C.POINTER(c_f32),
                                            C.POINTER(c_f32), c_i32, C.POINTER(c_i32), C.POINTER(c_vp), C.POINTER(c_i32), C.POINTER(c_i32)]),
     'hvx_op_mel_cache_append': (c_i32, [c_vp, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_vp), C.POINTER(c_i32), C.POINTER(c_i32), c_vp]),
+    'hvx_flow_stream_state_bytes': (c_sz, [c_vp, c_i32, c_i32]),
+    'hvx_flow_stream_workspace_bytes': (c_sz, [c_vp, c_i32, c_i32]),
+    'hvx_flow_stream_bind': (c_i32, [c_vp, c_vp, c_sz, c_i32, c_i32, C.POINTER(c_f32), c_i32]),
+    'hvx_flow_stream_reset': (c_i32, [c_vp, c_vp, c_vp]),
+    'hvx_flow_stream_info': (c_i32, [c_vp, c_vp, C.POINTER(c_i32)]),
+    'hvx_flow_stream_set_fill': (c_i32, [c_vp, c_vp, c_i32]),
+    'hvx_flow_stream_release': (c_i32, [c_vp, c_vp]),
+    'hvx_cfm_solve_incremental_batch': (c_i32, [c_vp, c_vp, c_vp, c_sz, c_i32, c_i32, C.POINTER(c_vp), C.POINTER(c_i32), c_vp, c_vp, c_vp, c_vp, c_i32,
+                                                C.POINTER(c_f32), C.POINTER(c_f32), c_i32, C.POINTER(c_i32), C.POINTER(c_vp), C.POINTER(c_i32), C.POINTER(c_i32)]),
+    'hvx_op_attention_window': (c_i32, [C.POINTER(AttnWindowArgs), c_vp]),
+    'hvx_op_attention_window_splits': (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
+    'hvx_op_kv_window_append': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_vp), C.POINTER(c_vp), C.POINTER(c_i64), C.POINTER(c_i32), C.POINTER(c_i32),
+                                        C.POINTER(c_i32), c_vp]),
     'hvx_cfm_solve': (c_i32, [c_vp, c_vp, c_vp, c_sz, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, C.POINTER(c_f32), C.POINTER(c_f32)]),
     'hvx_matcha_create': (c_i32, [C.POINTER(MatchaConfig), C.POINTER(c_vp), c_i32, C.POINTER(c_vp)]),
     'hvx_matcha_destroy': (None, [c_vp]),
@@ -281,6 +301,8 @@ SYMBOLS = {
 # per-sequence head counts (hvx_ras_sample_mixed, hvx_llm_decode_steps_mixed, hvx_llm_decode_join_mixed and hvx_seq_heads), and the streaming batch of the
 # serving engine (hvx_cfm_solve_stream_batch, hvx_op_mel_cache_append), and hvx_llm_decode_leave (a cancelled request's slot is retired on the stream).
 # The streaming vocoder (hvx_hift_left_context, hvx_hift_stream_*) joined at 8 the same additive way.
+# So did the incremental streaming flow (hvx_flow_stream_*, hvx_cfm_solve_incremental_batch, hvx_op_attention_window[_splits] with its own argument struct,
+# hvx_op_kv_window_append): no existing struct or symbol touched.
 # 8: the epi / q / k / vT / heads / t_pad / rope_* / q_scale / qkv_f16 fields of hvx_gemm_args, for the parity tests of the fused QKV epilogue (ops.qkv_gemm).
 HVX_ABI_VERSION = 8
 

@@ -62,6 +62,7 @@ __global__ __launch_bounds__(64 * NWV) void attn_fwd_kernel(AttnArgs a) {
     const int kv_len = a.kv_len ? a.kv_len[b] : a.kv_len_const;
     const int pos0 = (a.causal && a.pos0) ? a.pos0[b] : 0;
     const int n_valid_lo = a.n_valid_lo ? a.n_valid_lo[b] : a.kn;
+    const int roff = a.row_off ? a.row_off[b] : a.row_off_const;      // windowed rows: the chunk mask counts from the absolute row
     int key_begin = 0, key_end = kv_len;
     if (a.n_splits > 1) {
         key_begin = sp * a.split_chunk;
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(64 * NWV) void attn_fwd_kernel(AttnArgs a) {
             qf[i][0] = load8(qp);
             qf[i][1] = load8(qp + 32);
             max_pos = max(max_pos, pos0 + r_lo[i]);
-            if (a.chunk > 0) max_lim = max(max_lim, (r_lo[i] / a.chunk + 1) * a.chunk);
+            if (a.chunk > 0) max_lim = max(max_lim, ((r_lo[i] + roff) / a.chunk + 1) * a.chunk);
         } else {
             qf[i][0] = zero8<T>();
             qf[i][1] = zero8<T>();
@@ -187,7 +188,7 @@ __global__ __launch_bounds__(64 * NWV) void attn_fwd_kernel(AttnArgs a) {
                 }
                 // scale, mask, running max
                 int lim = a.causal ? min(key_end, pos0 + r_lo[i] + 1) : key_end;
-                if (a.chunk > 0) lim = min(lim, (r_lo[i] / a.chunk + 1) * a.chunk);
+                if (a.chunk > 0) lim = min(lim, ((r_lo[i] + roff) / a.chunk + 1) * a.chunk);
                 float sv[8];
                 float mx = -INFINITY;
 #pragma unroll
@@ -887,6 +888,240 @@ __global__ __launch_bounds__(256, 2) void attn_dit_kernel(AttnArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Windowed DiT form (incremental streaming flow; AttnArgs.window): 50 to ~200 query rows — rows row_off .. of their sequence — against a cache of up to
+// thousands of keys.  The DiT tile above needs 256 rows to fill a workgroup and one workgroup per 128 rows would leave most CUs idle, so the launch is
+// flash-decoding shaped: a workgroup is ONE KEY SPLIT (split_chunk keys, a multiple of 64) x up to 128 window rows.  Its four waves own 32 rows each and share
+// every 64-key K / V^T tile through LDS, staged and double-buffered exactly as attn_dit_kernel stages them (same row stride, same V^T key permutation).  The
+// softmax is the classical online one on exp2 (running maximum per row): a split may hold no visible key at all for some of its rows, which the reference-free
+// forms cannot represent.  Tiles wholly below the chunk limit of the workgroup's first row run unmasked; the others compare every score's key with its row's
+// limit min(kv_len, split end, ((row_off + r) / chunk + 1) * chunk).  (m, l, o) go to part_ml / part_o in attn_combine_kernel's layout (m in natural-log units).
+// ---------------------------------------------------------------------------------------------------------------------
+template <class T>
+__global__ __launch_bounds__(256, 2) void attn_window_kernel(AttnArgs a) {
+    typedef typename Vec8<T>::type T8;
+    typedef typename Vec4<T>::type T4;
+    constexpr int QR = 2, KT = 64, LD = 72, WG_ROWS = 64 * QR, NLD = 2;
+    __shared__ __attribute__((aligned(16))) T Ks[2][KT * LD];
+    __shared__ __attribute__((aligned(16))) T Vs[2][64 * LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fg = lane >> 4;
+    const int n_rb = (a.n_rows + WG_ROWS - 1) / WG_ROWS;
+    const int sp = blockIdx.x / n_rb, rb = blockIdx.x - sp * n_rb;
+    const int h = blockIdx.y, b = blockIdx.z;
+    const int kv_len = min(a.kv_len ? a.kv_len[b] : a.kv_len_const, a.kv_len_const);      // (a device length can not be refused at launch: never past the host's bound, which is <= v_ld)
+    const int roff = a.row_off ? a.row_off[b] : a.row_off_const;
+    const int key_begin = sp * a.split_chunk;
+    if (key_begin >= kv_len) return;                                   // (attn_combine_kernel reads the first ceil(kv_len / split_chunk) splits only)
+    const int key_end = min(kv_len, key_begin + a.split_chunk);
+    const int slot = a.kv_slot ? a.kv_slot[b] : b;
+    const T* __restrict__ kb = reinterpret_cast<const T*>(a.k) + (long long)slot * a.k_bs + (long long)h * a.k_hs;
+    const T* __restrict__ vb = reinterpret_cast<const T*>(a.vT) + (long long)slot * a.v_bs + (long long)h * a.v_hs;
+    const int wg_row0 = rb * WG_ROWS, wg_row1 = min(wg_row0 + WG_ROWS, a.n_rows) - 1;
+    const int row0 = wg_row0 + wave * (16 * QR);
+    auto row_lim = [&](int r) { return a.chunk > 0 ? min(key_end, ((r + roff) / a.chunk + 1) * a.chunk) : key_end; };
+    const int lim_hi = row_lim(wg_row1), lim_lo = row_lim(wg_row0);
+    int lim[QR];
+#pragma unroll
+    for (int i = 0; i < QR; ++i) lim[i] = row_lim(row0 + i * 16 + fr);
+
+    T8 qf[QR][2];
+#pragma unroll
+    for (int i = 0; i < QR; ++i) {
+        const int r = row0 + i * 16 + fr;
+        if (r < a.n_rows) {
+            const T* qp = reinterpret_cast<const T*>(a.q) + (long long)b * a.q_bs + (long long)h * a.q_hs + (long long)r * a.q_lo + fg * 8;
+            qf[i][0] = load8(qp);
+            qf[i][1] = load8(qp + 32);
+        } else {
+            qf[i][0] = zero8<T>();
+            qf[i][1] = zero8<T>();
+        }
+    }
+    // tile loader and V^T permutation: attn_dit_kernel's
+    const int lrow = tid >> 3, lchunk = (tid & 7) * 8;
+    T8 rk[NLD], rv[NLD];
+    auto gload = [&](int key0) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            int key = key0 + lrow + i * 32;
+            key = key < kv_len ? key : kv_len - 1;                       // clamped rows are masked below
+            rk[i] = load8(kb + (long long)key * 64 + lchunk);
+            rv[i] = load8(vb + (long long)(lrow + i * 32) * a.v_ld + key0 + lchunk);      // (key0 + 64 <= v_ld: v_ld % 64 == 0 and key0 < kv_len <= v_ld)
+        }
+    };
+    const int vc = tid & 7;
+    const int vpos = (vc >> 2) * 32 + ((vc & 1) * 2) * 8 + ((vc >> 1) & 1) * 4;
+    auto stash = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            store8(&Ks[buf][(lrow + i * 32) * LD + lchunk], rk[i]);
+            T4 lo, hi;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                lo[j] = rv[i][j];
+                hi[j] = rv[i][4 + j];
+            }
+            *reinterpret_cast<T4*>(&Vs[buf][(lrow + i * 32) * LD + vpos]) = lo;
+            *reinterpret_cast<T4*>(&Vs[buf][(lrow + i * 32) * LD + vpos + 8]) = hi;
+        }
+    };
+
+    float m_run[QR], l_acc[QR];
+    f32x4 o_acc[QR][4];
+#pragma unroll
+    for (int i = 0; i < QR; ++i) {
+        m_run[i] = -INFINITY;
+        l_acc[i] = 0.0f;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o_acc[i][dt] = f32x4{0, 0, 0, 0};
+    }
+    const float c = a.q_log2 ? 1.0f : a.scale * 1.4426950408889634f;    // scores in log2 units
+    T8 ones;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ones[e] = (T)1.0f;
+
+    auto tile = [&](int buf, int key0, auto tail_tag) {
+        constexpr bool TAIL = decltype(tail_tag)::value;
+        f32x4 s[QR][4];
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+            const T8 k0 = load8(&Ks[buf][(kt * 16 + fr) * LD + fg * 8]);
+            const T8 k1 = load8(&Ks[buf][(kt * 16 + fr) * LD + 32 + fg * 8]);
+#pragma unroll
+            for (int i = 0; i < QR; ++i) {
+                s[i][kt] = f32x4{0, 0, 0, 0};
+                mma32(s[i][kt], k0, qf[i][0]);
+                mma32(s[i][kt], k1, qf[i][1]);
+            }
+        }
+        T8 pf[QR][2];
+#pragma unroll
+        for (int i = 0; i < QR; ++i) {
+            if constexpr (TAIL) {
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (key0 + kt * 16 + fg * 4 + r >= lim[i]) s[i][kt][r] = -INFINITY;
+            }
+            float mx = fmax3(fmax3(s[i][0][0], s[i][0][1], s[i][0][2]), fmax3(s[i][0][3], s[i][1][0], s[i][1][1]), fmax3(s[i][1][2], s[i][1][3], s[i][2][0]));
+            mx = fmax3(mx, fmax3(s[i][2][1], s[i][2][2], s[i][2][3]), fmax3(s[i][3][0], s[i][3][1], s[i][3][2]));
+            mx = fmax2(mx, s[i][3][3]);
+            mx = fmax2(mx, __shfl_xor(mx, 16, 64));
+            mx = fmax2(mx, __shfl_xor(mx, 32, 64));
+            const float m_new = fmax2(m_run[i], mx * c);               // c > 0
+            const float m_safe = (m_new == -INFINITY) ? 0.0f : m_new;  // a row that has seen no key yet: p = exp2(-inf) = 0, never exp2(-inf + inf)
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        pf[i][m][4 * hh + r] = (T)__builtin_amdgcn_exp2f(__builtin_fmaf(s[i][2 * m + hh][r], c, -m_safe));
+            if (__any(m_new != m_run[i])) {                              // wave-uniform
+                const float alpha = __builtin_amdgcn_exp2f(m_run[i] - m_safe);      // exp2(-inf) == 0 on the row's first visible tile
+                l_acc[i] *= alpha;
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) o_acc[i][dt] *= alpha;
+                m_run[i] = m_new;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < QR; ++i) {
+            f32x4 lt = {0, 0, 0, 0};                                     // the row sums on the matrix cores: exactly the probabilities that multiply V
+            mma32(lt, ones, pf[i][0]);
+            mma32(lt, ones, pf[i][1]);
+            l_acc[i] += lt[0];
+        }
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const T8 v = load8(&Vs[buf][(dt * 16 + fr) * LD + m * 32 + fg * 8]);
+#pragma unroll
+                for (int i = 0; i < QR; ++i) mma32(o_acc[i][dt], v, pf[i][m]);
+            }
+    };
+
+    const int n_tiles = lim_hi > key_begin ? (lim_hi - key_begin + KT - 1) / KT : 0;
+    const int n_full = lim_lo > key_begin ? min(n_tiles, (lim_lo - key_begin) / KT) : 0;     // unmasked tiles first
+    if (n_tiles > 0) {
+        gload(key_begin);
+        stash(0);
+    }
+    __syncthreads();
+    for (int it = 0; it < n_tiles; ++it) {
+        const int buf = it & 1, key0 = key_begin + it * KT;
+        const bool more = (it + 1) < n_tiles;
+        if (more) gload(key0 + KT);
+        if (it < n_full) tile(buf, key0, std::false_type{});
+        else tile(buf, key0, std::true_type{});
+        if (more) stash(buf ^ 1);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < QR; ++i) {
+        const int r = row0 + i * 16 + fr;
+        if (r >= a.n_rows) continue;
+        const long long base = (((long long)b * a.heads + h) * a.n_splits + sp) * a.n_rows_pad + r;
+        float* po = a.part_o + base * 64;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(po + dt * 16 + fg * 4) = o_acc[i][dt];
+        if (fg == 0) {
+            a.part_ml[base * 2 + 0] = m_run[i] * 0.6931471805599453f;      // (-inf stays -inf: a split without a visible key for this row)
+            a.part_ml[base * 2 + 1] = l_acc[i];
+        }
+    }
+}
+
+// split count and length of a windowed launch: splits x row blocks x heads x batch entries of about two workgroups per CU, split length a multiple of 64
+int attention_window_splits(int dtype, int batch, int heads, int n_rows, int kv_max, int max_splits, int* split_chunk) {
+    static int n_cu = 0;
+    if (n_cu == 0) {
+        int dev = 0, v = 0;
+        n_cu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+    }
+    const int rows_wg = dtype == DT_F32 ? 64 : 128;                   // (fp32: four one-tile waves of the generic kernel per workgroup)
+    const long long base = (long long)((n_rows + rows_wg - 1) / rows_wg) * heads * batch;
+    long long want = (2LL * n_cu + base - 1) / base;
+    want = want < 1 ? 1 : (want > max_splits ? max_splits : want);
+    int sc = (int)(((kv_max + want - 1) / want + 63) / 64 * 64);
+    if (sc < 64) sc = 64;
+    if (split_chunk) *split_chunk = sc;
+    return (kv_max + sc - 1) / sc;
+}
+
+template <class T>
+static int launch_window(const AttnArgs& a_in, hipStream_t s) {
+    AttnArgs a = a_in;
+    if (a.causal || a.kv_frag || a.o_frag_kt > 0 || a.n_valid_lo || a.kn < a.n_rows || (a.v_ld & 63) || a.kv_len_const < 1 || a.kv_len_const > a.v_ld || !a.part_o ||
+        !a.part_ml || a.n_rows_pad < a.n_rows || a.n_splits < 1 || a.split_chunk < 0 || (a.split_chunk & 63) || a.row_off_const < 0)
+        return set_error("launch_attention: windowed form: non-causal, one row group, v_ld %% 64 == 0, 1 <= kv_len <= v_ld, partial buffers, split_chunk %% 64 == 0"), -1;
+    const int cap_splits = a.n_splits;
+    // fp32 is the parity mode: left to itself it takes ONE split, i.e. the generic kernel's walk over all keys in the whole-prefix path's order — a row's attention is then
+    // bit-identical to that path's; an explicit split_chunk splits it like the 16-bit form
+    if (a.split_chunk == 0 && sizeof(T) == 4) a.split_chunk = (a.kv_len_const + 63) & ~63, a.n_splits = 1;
+    else if (a.split_chunk == 0) a.n_splits = attention_window_splits(a.dtype, a.batch, a.heads, a.n_rows, a.kv_len_const, cap_splits, &a.split_chunk);
+    else a.n_splits = (a.kv_len_const + a.split_chunk - 1) / a.split_chunk;
+    if (a.n_splits > cap_splits) return set_error("launch_attention: windowed form: %d splits of %d keys, room for %d", a.n_splits, a.split_chunk, cap_splits), -1;
+    a.sub_chunk = 0;
+    a.skip_combine = 0;
+    const int slot = prof_begin(PK_ATTN, 0.0, s);
+    if constexpr (sizeof(T) == 2) {
+        const int n_rb = (a.n_rows + 127) / 128;
+        hipLaunchKernelGGL((attn_window_kernel<T>), dim3(a.n_splits * n_rb, a.heads, a.batch), dim3(256), 0, s, a);
+    } else {
+        if (a.q_log2) a.scale = 0.6931471805599453f;
+        const int n_qt = (a.n_rows + 15) / 16;
+        hipLaunchKernelGGL((attn_fwd_kernel<T, 1, false, false>), dim3((n_qt * a.n_splits + 3) / 4, a.heads, a.batch), dim3(256), 0, s, a);
+    }
+    // (one split in fp32: the generic kernel has written the rows themselves)
+    if (sizeof(T) == 2 || a.n_splits > 1) hipLaunchKernelGGL((attn_combine_kernel<T>), dim3((a.n_rows + 3) / 4, a.heads, a.batch), dim3(256), 0, s, a);
+    prof_end(slot, s);
+    return hipGetLastError() == hipSuccess ? 0 : (set_error("attention launch failed"), -1);
+}
+
 template <class T>
 static int launch_t(const AttnArgs& a_in, hipStream_t s) {
     AttnArgs a = a_in;
@@ -975,6 +1210,10 @@ int launch_attention(const AttnArgs& a_in, hipStream_t s) {
     if (a.n_splits < 1) a.n_splits = 1;
 
     if (a.kn < 1) a.kn = a.n_rows;
+    if (a.window) {
+        if (a.dtype != DT_BF16 && a.dtype != DT_F32) return set_error("launch_attention: the windowed form takes bf16 or fp32 operands"), -1;
+        return a.dtype == DT_BF16 ? launch_window<bf16_t>(a, s) : launch_window<float>(a, s);
+    }
     if (a.n_sub != 8 || !a.kv_frag || a.n_rows > 16 || a.dtype != DT_BF16) a.n_sub = 4;       // (the 8-wave form exists for the one-tile bf16 decode over fragment-order caches)
     if (a.n_splits == 1 || a.n_rows > 32 || a.sub_chunk * a.n_sub != a.split_chunk || (a.sub_chunk & 31)) a.sub_chunk = 0;
     if (a.kv_frag && (a.chunk > 0 || !a.causal)) return set_error("launch_attention: fragment-order caches serve the causal LLM calls only"), -1;

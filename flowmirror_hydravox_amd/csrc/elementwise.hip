@@ -646,6 +646,40 @@ int launch_mel_cache_append(const float* x, int n, int mel, int t_max, const int
     return 0;
 }
 
+// Incremental flow: the window's K rows and V^T columns into the sessions' caches (hvx_kernels.h: KvAppendArgs).  A block moves a 64-row x 64-channel tile of one
+// (entry, head): K with the channel fastest, V^T with the row fastest, element by element — r0 is a multiple of the chunk (50), not of a vector of keys.
+template <class E>
+__global__ __launch_bounds__(256) void kv_window_append_kernel(KvAppendArgs a) {
+    const int e = blockIdx.z, i = e >> 1, br = e & 1, h = blockIdx.y, w0 = blockIdx.x * 64;
+    const int rows = a.rows[i], cap = a.cap[i], r0 = a.r0[i];
+    if (w0 >= rows) return;
+    const E* sk = reinterpret_cast<const E*>(a.k) + ((long long)e * a.heads + h) * a.t_pad * 64;
+    const E* sv = reinterpret_cast<const E*>(a.vT) + ((long long)e * a.heads + h) * 64 * a.t_pad;
+    E* dk = reinterpret_cast<E*>(a.dk[i]) + br * a.bs[i] + (long long)h * cap * 64;
+    E* dv = reinterpret_cast<E*>(a.dv[i]) + br * a.bs[i] + (long long)h * 64 * cap;
+    for (int lin = threadIdx.x; lin < 64 * 64; lin += 256) {
+        const int hi = lin >> 6, lo = lin & 63;
+        if (w0 + hi < rows) dk[(long long)(r0 + w0 + hi) * 64 + lo] = sk[(long long)(w0 + hi) * 64 + lo];
+        if (w0 + lo < rows) dv[(long long)hi * cap + r0 + w0 + lo] = sv[(long long)hi * a.t_pad + w0 + lo];
+    }
+}
+int launch_kv_window_append(const KvAppendArgs& a, hipStream_t s) {
+    if (!a.k || !a.vT || a.n < 1 || a.n > MEL_APPEND_MAX || a.heads < 1 || a.t_pad < 1 || (a.es != 2 && a.es != 4))
+        return set_error("kv_window_append: bad arguments (n=%d, heads=%d, t_pad=%d, es=%d)", a.n, a.heads, a.t_pad, a.es), -1;
+    int widest = 0;
+    for (int i = 0; i < a.n; ++i) {
+        if (!a.dk[i] || !a.dv[i]) return set_error("kv_window_append: session %d has no cache", i), -1;
+        if (a.rows[i] < 0 || a.r0[i] < 0 || a.rows[i] > a.t_pad || (long long)a.r0[i] + a.rows[i] > a.cap[i])
+            return set_error("kv_window_append: session %d: rows [%d, %d + %d) leave a cache of %d (window of %d)", i, a.r0[i], a.r0[i], a.rows[i], a.cap[i], a.t_pad), -1;
+        if (a.rows[i] > widest) widest = a.rows[i];
+    }
+    if (widest == 0) return 0;
+    const dim3 grid((widest + 63) / 64, a.heads, 2 * a.n);
+    if (a.es == 2) hipLaunchKernelGGL(kv_window_append_kernel<unsigned short>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(kv_window_append_kernel<unsigned>, grid, dim3(256), 0, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : (set_error("kv_window_append launch failed"), -1);
+}
+
 template <class D>
 __global__ void rows_to_dtype_kernel(const float* src, int ld_src, D* dst, int ld_dst, int cols, int cols_pad) {
     const int r = blockIdx.x;

@@ -314,6 +314,46 @@ int hvx_op_mel_cache_append(const float* x, int32_t n, int32_t mel, int32_t t_ma
     return launch_mel_cache_append(x, n, mel, t_max, t_len, covered, cache, cache_ld, cache_fill, (hipStream_t)s);      // (refuses before it launches)
 }
 
+int hvx_op_attention_window(const hvx_attn_window_args* a, hvx_stream s) {
+    if (!a) return set_error("hvx_op_attention_window: null args"), -1;
+    if (!a->q || !a->out || !a->k || !a->vT || !a->part_o || !a->part_ml) return set_error("hvx_op_attention_window: null q, out, k, vT or partial buffer"), -1;
+    if (a->batch < 1 || a->heads < 1 || a->rows < 1 || a->q_pad < a->rows || a->max_splits < 1)
+        return set_error("hvx_op_attention_window: batch=%d heads=%d rows=%d q_pad=%d max_splits=%d", a->batch, a->heads, a->rows, a->q_pad, a->max_splits), -1;
+    AttnArgs k;
+    memset(&k, 0, sizeof(k));
+    const long long D = (long long)a->heads * 64;
+    k.dtype = a->dtype; k.batch = a->batch; k.heads = a->heads; k.n_rows = a->rows; k.kn = a->rows;
+    k.q = a->q; k.q_bs = (long long)a->heads * a->q_pad * 64; k.q_hs = (long long)a->q_pad * 64; k.q_lo = 64;
+    k.k = a->k; k.k_bs = a->slot_stride; k.k_hs = (long long)a->cap * 64;
+    k.vT = a->vT; k.v_bs = a->slot_stride; k.v_hs = (long long)64 * a->cap; k.v_ld = a->cap;
+    k.kv_slot = a->kv_slot; k.kv_len = a->kv_len; k.kv_len_const = a->kv_max; k.chunk = a->chunk > 0 ? a->chunk : 0; k.scale = a->scale; k.q_log2 = a->q_log2;
+    k.row_off = a->r0; k.row_off_const = a->r0_const; k.window = 1;
+    k.out = a->out; k.o_bs = (long long)a->rows * D; k.o_hs = 64; k.o_lo = D;
+    k.n_splits = a->max_splits; k.split_chunk = a->split_chunk; k.part_o = a->part_o; k.part_ml = a->part_ml; k.n_rows_pad = (a->rows + 31) & ~31;
+    return launch_attention(k, (hipStream_t)s);
+}
+
+int hvx_op_attention_window_splits(int32_t dtype, int32_t batch, int32_t heads, int32_t rows, int32_t kv_max, int32_t max_splits, int32_t* split_chunk) {
+    if (batch < 1 || heads < 1 || rows < 1 || kv_max < 1 || max_splits < 1) return set_error("hvx_op_attention_window_splits: bad shape"), -1;
+    int sc = 0;
+    const int n = attention_window_splits(dtype, batch, heads, rows, kv_max, max_splits, &sc);
+    if (split_chunk) *split_chunk = sc;
+    return n;
+}
+
+int hvx_op_kv_window_append(const void* k, const void* vT, int32_t es, int32_t heads, int32_t t_pad, int32_t n, void* const* dk, void* const* dv,
+                            const int64_t* branch_stride, const int32_t* cap, const int32_t* r0, const int32_t* rows, hvx_stream s) {
+    if (!dk || !dv || !branch_stride || !cap || !r0 || !rows) return set_error("hvx_op_kv_window_append: null argument"), -1;
+    if (n < 1 || n > MEL_APPEND_MAX) return set_error("hvx_op_kv_window_append: %d sessions outside [1, %d]", n, MEL_APPEND_MAX), -1;
+    KvAppendArgs a;
+    memset(&a, 0, sizeof(a));
+    a.k = k; a.vT = vT; a.es = es; a.heads = heads; a.t_pad = t_pad; a.n = n;
+    for (int i = 0; i < n; ++i) {
+        a.dk[i] = dk[i]; a.dv[i] = dv[i]; a.bs[i] = branch_stride[i]; a.cap[i] = cap[i]; a.r0[i] = r0[i]; a.rows[i] = rows[i];
+    }
+    return launch_kv_window_append(a, (hipStream_t)s);
+}
+
 int hvx_op_skinny_gemm(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* Wpacked, const float* bias,
                        int32_t split_k, float* part_ws, float* out_f32, int32_t ldo, hvx_stream s) {
     if (dtype != DT_F32 && dtype != DT_BF16) return set_error("hvx_op_skinny_gemm: dtype %d: fp32 (0) or bf16 (1) only", dtype), -1;

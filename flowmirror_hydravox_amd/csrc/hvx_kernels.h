@@ -165,8 +165,17 @@ struct AttnArgs {
                                                       // per (batch, head) block of k_hs / v_hs elements); v_ld = the cache's context capacity
     int o_frag_kt;                                    // > 0 (LLM decode, 16-bit): out is the [batch * kn][heads * rows_hi * 64] activation matrix in fragment
                                                       // order (hvx_device.h: frag_index) with this many k-steps per row; the o_* strides are ignored
+    // ---- windowed DiT form (incremental streaming flow): the n_rows query rows are rows row_off .. row_off + n_rows - 1 of a sequence whose keys [0, kv_len) sit in a
+    //      cache ([.][heads][v_ld][64] / [.][heads][64][v_ld], v_ld % 64 == 0, kv_len <= v_ld); the chunk mask uses the ABSOLUTE row: key j < ((row_off + r) / chunk + 1) * chunk
+    const int* row_off;                               // optional device [batch]; else row_off_const (0: the rows start the sequence, every other form)
+    int row_off_const;
+    int window;                                       // != 0: split the keys over workgroups (attn_window_kernel for 16-bit operands, the generic kernel for fp32) and combine.
+                                                      // n_splits = the most splits part_o / part_ml hold, split_chunk = keys per split (multiple of 64) or 0: chosen per launch
+                                                      // from kv_len_const, which must be the LONGEST kv_len of the launch
 };
 int launch_attention(const AttnArgs& a, hipStream_t s);
+int attention_window_splits(int dtype, int batch, int heads, int n_rows, int kv_max, int max_splits, int* split_chunk);   // the split count / length launch_attention chooses
+
 
 // ------------------------------------------------------------------------------------------------
 // Small fused kernels
@@ -251,6 +260,15 @@ int check_mel_cache_append(const char* who, int n, int mel, int t_max, const int
                            const int* cache_fill);
 int launch_mel_cache_append(const float* x, int n, int mel, int t_max, const int* t_len, const int* covered, float* const* cache, const int* cache_ld,
                             const int* cache_fill, hipStream_t s);
+// Window K / V^T of the QKV epilogue ([entries][heads][t_pad][64] / [entries][heads][64][t_pad], entries = 2 i + branch) -> rows / columns [r0[i], r0[i] + rows[i]) of session
+// i's caches: dk[i] / dv[i] point at branch 0's [heads][cap[i]][64] / [heads][64][cap[i]], branch 1's lie bs[i] elements behind.  Host arrays, by value; es = bytes per element.
+struct KvAppendArgs {
+    const void* k; const void* vT; int es, heads, t_pad, n;
+    void* dk[MEL_APPEND_MAX]; void* dv[MEL_APPEND_MAX];
+    long long bs[MEL_APPEND_MAX];
+    int cap[MEL_APPEND_MAX], r0[MEL_APPEND_MAX], rows[MEL_APPEND_MAX];
+};
+int launch_kv_window_append(const KvAppendArgs& a, hipStream_t s);       // refuses (before launching) rows that leave a cache
 
 // ------------------------------------------------------------------------------------------------
 // Sampler (common.py:138-166 + llm_multi_head_v3.py:151-166, 890-900)

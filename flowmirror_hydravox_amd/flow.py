@@ -47,6 +47,69 @@ def euler_schedule(n_timesteps):
 FLOW_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
 
+def window_rule(covered, T, chunk, fill=None):
+    """The incremental flow's window for a job of T frames of which `covered` are handed out: (r0, rows) — rows [r0, T) are solved, r0 the last chunk boundary at or
+    below `covered` (rows below it repeat in every longer solve; rows of a partial chunk do not, so [r0, covered) is solved again and dropped).  fill: frames of the
+    state's last prefix, when known — an empty state (0) takes the whole prefix whatever is covered (a prompt's frames are covered from the start)."""
+    covered, T, chunk = int(covered), int(T), int(chunk)
+    if chunk <= 0 or covered < 0 or T <= covered or (fill is not None and 0 < fill < covered):
+        raise ValueError('window_rule: chunk=%d, covered=%d, T=%d, fill=%s' % (chunk, covered, T, fill))
+    r0 = 0 if fill == 0 else covered // chunk * chunk
+    return r0, T - r0
+
+
+def flow_stream_state_bytes(cfg, dtype, max_frames, n_steps):
+    """bytes of a FlowStream state (include/hvx.h: hvx_flow_stream_state_bytes): K [heads][cap][64] + V^T [heads][64][cap] of every (step, block, CFG branch) in the
+    attention's operand type, then the x-trajectory [n_steps][mel][cap] fp32; cap = max_frames rounded up to 64"""
+    cap = (int(max_frames) + 63) // 64 * 64
+    es = 4 if dtype == torch.float32 else 2
+    return n_steps * cfg.depth * 2 * 2 * cfg.heads * cap * 64 * es + n_steps * cfg.mel * cap * 4
+
+
+class FlowStream:
+    """Per-utterance state of the incremental flow (HvxFlow.stream): the K / V^T caches and the x-trajectory of one utterance's chunk-masked solves, in one device
+    tensor, plus what the host knows of it.  `fill`: frames of the last prefix solved; `rows_solved`: window rows solved so far (a whole-prefix path would have solved
+    the sum of the prefixes).  release() frees the tensor and unregisters it from the flow handle."""
+
+    def __init__(self, flow, max_frames, n_timesteps=None):
+        self.flow = flow
+        self.n_timesteps = int(n_timesteps or flow.cfg.n_timesteps)
+        self.max_frames = int(max_frames)
+        self.chunk = int(flow.static_chunk_size)
+        need = flow.lib.hvx_flow_stream_state_bytes(flow._h, self.max_frames, self.n_timesteps)
+        if need == 0:
+            raise _lib.HvxError('FlowStream: max_frames=%d, n_timesteps=%d' % (self.max_frames, self.n_timesteps))
+        self.state = torch.empty(need, dtype=torch.uint8, device=flow.device)
+        ts, _ = euler_schedule(self.n_timesteps)
+        check(flow.lib.hvx_flow_stream_bind(flow._h, ptr(self.state), need, self.max_frames, self.n_timesteps, (C.c_float * self.n_timesteps)(*ts), self.chunk),
+              'hvx_flow_stream_bind')
+        self.fill = 0
+        self.rows_solved = 0
+        self.reset()
+
+    def reset(self):
+        """a new utterance in the same memory"""
+        check(self.flow.lib.hvx_flow_stream_reset(self.flow._h, stream_ptr(), ptr(self.state)), 'hvx_flow_stream_reset')
+        self.fill = 0
+        self.rows_solved = 0
+
+    def release(self):
+        if self.state is not None:
+            try:
+                if getattr(self.flow, '_h', None) is not None:
+                    self.flow.lib.hvx_flow_stream_release(self.flow._h, ptr(self.state))
+            finally:
+                self.state = None
+
+    close = release
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 def packed_flow_dtype(ws, depth):
     """The flow mode a packed weight list (HvxFlow.pack_state_dict) was made for.  The tell is the attention out-projection of block 0 (weights[23]): it is
     packed in the handle's dtype in every mode — fp32, bf16 (also with fp16 block Linears, whose QKV / FF matrices are fp16 while this one stays bf16), fp16."""
@@ -351,6 +414,55 @@ class HvxFlow:
         check(self.lib.hvx_cfm_solve_stream_batch(self._h, stream_ptr(), ptr(ws), ws.numel(), n_utt, T, None if not lens or min(lens) == T else tl, ptr(x), ptr(mu),
                                                   ptr(spk), ptr(cond), n, ta, da, self.static_chunk_size if flags and flags[0] else 0, cov, pa, ld, fill),
               'hvx_cfm_solve_stream_batch')
+        return [lens[i] - int(covered[i]) for i in range(n_utt)]
+
+    def stream(self, max_frames, n_timesteps=None):
+        """a FlowStream for one utterance of up to max_frames mel frames (prompt included).  Its state takes flow_stream_state_bytes: 1.76 MB per frame at CV3
+        dimensions in bf16 (3.6 GB at 2048 frames)."""
+        if self.fp16:
+            raise _lib.HvxError('the incremental flow serves bf16 and fp32 handles, not the fp16 mode')
+        return FlowStream(self, max_frames, n_timesteps)
+
+    def solve_incremental_batch(self, streams, mus, spks, conds, covered, caches, cache_fill, n_timesteps=None):
+        """solve_stream_batch(streaming=True) for sessions that own a FlowStream (hvx_cfm_solve_incremental_batch): session i's prefix mu / cond (mel, T_i) are given whole,
+        as there, but only rows [r0_i, T_i) — window_rule(covered[i], T_i, static_chunk_size) — are solved, against the cached keys and values of the rows below; frames
+        [covered[i], T_i) go into caches[i] from column cache_fill[i] on.  Up to 16 sessions per call (more: further calls).  Returns the frames appended per session."""
+        from .ops import mel_append_block
+        n_utt = len(mus)
+        if n_utt > 16:
+            out = []
+            for a in range(0, n_utt, 16):
+                sl = slice(a, a + 16)
+                out += self.solve_incremental_batch(streams[sl], mus[sl], spks[sl], conds[sl], covered[sl], caches[sl], cache_fill[sl], n_timesteps)
+            return out
+        lens = [int(m.shape[-1]) for m in mus]
+        T = max(lens) if lens else 0
+        mel, dev = self.cfg.mel, self.device
+        n = n_timesteps or self.cfg.n_timesteps
+        x = torch.zeros(n_utt, mel, T, dtype=torch.float32, device=dev)
+        mu = torch.zeros(n_utt, mel, T, dtype=torch.float32, device=dev)
+        cond = torch.zeros(n_utt, mel, T, dtype=torch.float32, device=dev)
+        for i in range(n_utt):
+            x[i, :, :lens[i]] = self.rand_noise[0, :, :lens[i]]
+            mu[i, :, :lens[i]] = mus[i]
+            cond[i, :, :lens[i]] = conds[i]
+        spk = torch.stack([s_.to(dev, torch.float32).view(-1) for s_ in spks]).contiguous() if n_utt else torch.zeros(0, mel, device=dev)
+        tl, cov, pa, ld, fill = mel_append_block(lens, covered, caches, cache_fill)
+        ts, dts = euler_schedule(n)
+        ta = (C.c_float * n)(*ts)
+        da = (C.c_float * n)(*dts)
+        chunk = self.static_chunk_size
+        rows = [lens[i] - (int(covered[i]) // chunk * chunk if chunk > 0 and streams[i].fill > 0 else 0) for i in range(n_utt)]
+        need = self.lib.hvx_flow_stream_workspace_bytes(self._h, max(n_utt, 1), max(rows + [1]))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._ws
+        sa = (C.c_void_p * max(n_utt, 1))(*[st.state.data_ptr() for st in streams])
+        check(self.lib.hvx_cfm_solve_incremental_batch(self._h, stream_ptr(), ptr(ws), ws.numel(), n_utt, T, sa, tl, ptr(x), ptr(mu), ptr(spk), ptr(cond), n, ta, da, chunk,
+                                                       cov, pa, ld, fill), 'hvx_cfm_solve_incremental_batch')
+        for i, st in enumerate(streams):
+            st.fill = lens[i]
+            st.rows_solved += rows[i]
         return [lens[i] - int(covered[i]) for i in range(n_utt)]
 
     @torch.inference_mode()

@@ -159,6 +159,60 @@ def attention(q, k, vT, t, *, kv_len=None, causal=False, scale=None, n_splits=1,
     return out
 
 
+def attention_window(q, k, vT, rows, *, r0, kv_len, kv_slot=None, chunk=0, scale=None, q_log2=False, split_chunk=0, max_splits=16):
+    """The windowed DiT attention (hvx_op_attention_window; csrc/attention.hip: attn_window_kernel for bf16, the generic kernel with key splits for fp32).
+    q: [B][H][q_pad][64], window-local rows; k: [S][H][cap][64] and vT: [S][H][64][cap], the caches of S slots; entry b reads slot kv_slot[b] (default b), its `rows`
+    query rows are rows r0[b] .. of the sequence and see keys j < min(kv_len[b], ((r0[b] + i) / chunk + 1) * chunk).  r0, kv_len: ints or lists per entry.
+    -> [B][rows][H*64]"""
+    lib = _lib.load()
+    B, H, qp, d = q.shape
+    S, cap = k.shape[0], k.shape[2]
+    assert d == 64 and k.shape == (S, H, cap, 64) and vT.shape == (S, H, 64, cap) and cap % 64 == 0 and k.is_contiguous() and vT.is_contiguous() and q.is_contiguous()
+    dev = q.device
+    as_list = lambda v: [int(v)] * B if isinstance(v, int) else [int(x) for x in v]
+    r0l, kvl = as_list(r0), as_list(kv_len)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+    keep = [i32(r0l), i32(kvl), None if kv_slot is None else i32([int(x) for x in kv_slot])]
+    out = torch.empty(B, rows, H * 64, dtype=q.dtype, device=dev)
+    rp = _pad32(rows)
+    po = torch.empty(B * H * max_splits * rp * 64, dtype=torch.float32, device=dev)
+    pm = torch.empty(B * H * max_splits * rp * 2, dtype=torch.float32, device=dev)
+    a = _lib.AttnWindowArgs()
+    a.dtype, a.batch, a.heads, a.rows, a.q_pad = dtype_code(q.dtype), B, H, int(rows), qp
+    a.q, a.out, a.k, a.vT, a.cap, a.slot_stride = ptr(q), ptr(out), ptr(k), ptr(vT), cap, H * cap * 64
+    a.kv_slot, a.r0, a.kv_len = ptr(keep[2]), ptr(keep[0]), ptr(keep[1])
+    a.r0_const, a.kv_max, a.chunk = 0, max(kvl), int(chunk)
+    a.scale, a.q_log2 = (1.0 / math.sqrt(64)) if scale is None else scale, int(q_log2)
+    a.split_chunk, a.max_splits, a.part_o, a.part_ml = int(split_chunk), int(max_splits), ptr(po), ptr(pm)
+    check(lib.hvx_op_attention_window(C.byref(a), stream_ptr()), 'hvx_op_attention_window')
+    return out
+
+
+def attention_window_splits(dtype, batch, heads, rows, kv_max, max_splits=16):
+    """(splits, keys per split) that attention_window(split_chunk=0) chooses for a shape: host arithmetic (needs no GPU beyond the CU count, 256 without one)"""
+    lib = _lib.load()
+    sc = C.c_int32(0)
+    n = lib.hvx_op_attention_window_splits(dtype_code(dtype), batch, heads, rows, kv_max, max_splits, C.byref(sc))
+    check(0 if n > 0 else -1, 'hvx_op_attention_window_splits')
+    return int(n), int(sc.value)
+
+
+def kv_window_append(k, vT, dk, dv, r0, rows):
+    """The cache append of the incremental flow (hvx_op_kv_window_append; csrc/elementwise.hip: kv_window_append_kernel).  k: [2n][H][t_pad][64], vT: [2n][H][64][t_pad]
+    (entry 2 i + branch); dk[i]: [2][H][cap_i][64] and dv[i]: [2][H][64][cap_i], session i's caches of both branches; rows [r0[i], r0[i] + rows[i]) of them are written."""
+    lib = _lib.load()
+    E, H, tp, d = k.shape
+    n = len(dk)
+    assert E == 2 * n and d == 64 and vT.shape == (E, H, 64, tp) and k.is_contiguous() and vT.is_contiguous()
+    for a_, b_ in zip(dk, dv):
+        assert a_.dtype == k.dtype and b_.dtype == k.dtype and a_.is_contiguous() and b_.is_contiguous() and a_.shape[0] == 2 and b_.shape == (2, H, 64, a_.shape[2])
+    pa = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    ia = lambda v: (C.c_int32 * n)(*[int(x) for x in v])
+    bs = (C.c_int64 * n)(*[int(t.shape[1] * t.shape[2] * 64) for t in dk])
+    check(lib.hvx_op_kv_window_append(ptr(k), ptr(vT), k.element_size(), H, tp, n, pa(dk), pa(dv), bs, ia([t.shape[2] for t in dk]), ia(r0), ia(rows), stream_ptr()),
+          'hvx_op_kv_window_append')
+
+
 def skinny_gemm(x, w_packed, n_out, bias=None, split_k=1):
     """x: [M][K] (f32/bf16), w_packed: pack_frag([N][K]) -> f32 [M][N]"""
     lib = _lib.load()

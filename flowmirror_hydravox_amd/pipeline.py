@@ -100,8 +100,10 @@ class _StreamUtterance:
     as state the batched acoustic stage can work on — the mel cache plane (sized from the utterance's token budget; `fill` frames are valid), the chunk
     schedule, the prompt arguments of the flow, the jobs that are ready and `handed`, the samples already handed out."""
 
-    def __init__(self, u, flow, hop, max_tokens, device, t_fetch, hift=None):
-        """hift: given with serve(incremental_vocoder=True) — the utterance owns a vocoder stream (hift.HiftStream) as long as its mel cache plane"""
+    def __init__(self, u, flow, hop, max_tokens, device, t_fetch, hift=None, incremental_flow=False):
+        """hift: given with serve(incremental_vocoder=True) — the utterance owns a vocoder stream (hift.HiftStream) as long as its mel cache plane.
+        incremental_flow: it owns a flow stream (flow.FlowStream: K / V^T caches and x-trajectory of its chunk-masked solves) for as long, sized for the prompt's
+        frames plus the plane"""
         from .streaming import ChunkSchedule
         pt = _flow_prompt(u)
         self.u = u
@@ -115,6 +117,7 @@ class _StreamUtterance:
         self.fill = 0
         self.handed = 0
         self.vstream = None if hift is None else hift.stream(min(int(self.cache.shape[1]), hift.max_stream_frames))
+        self.fstream = flow.stream(min(self.prompt_frames + int(self.cache.shape[1]), flow.max_t)) if incremental_flow else None
         self.jobs = []                   # (tokens in the piece, covered, final) not yet solved, in order
         self.pieces = 0
         self.tokens = None               # the utterance's full token list, once the LM has finished it
@@ -126,6 +129,15 @@ class _StreamUtterance:
         if self.vstream is not None:
             self.vstream.close()
             self.vstream = None
+        if self.fstream is not None:
+            self.fstream.release()
+            self.fstream = None
+
+    def window_rows(self, flow, n, covered):
+        """rows the incremental flow solves for the non-final job (n, covered): flow.window_rule over the job's frames and the flow stream's fill"""
+        from .flow import window_rule
+        ratio = flow.token_mel_ratio
+        return window_rule(self.prompt_frames + covered * ratio, ratio * (self.n_prompt + n - flow.pre_lookahead_len), flow.static_chunk_size, fill=self.fstream.fill)[1]
 
     def flow_inputs(self, flow, n, final):
         """mu, spk, cond of the flow over the prompt and the first n generated tokens (HvxFlow.inference's plumbing)"""
@@ -351,7 +363,7 @@ class HvxPipeline:
     @torch.inference_mode()
     def serve(self, source, lm_slots=16, acoustic_batch=None, acoustic_min_batch=1, max_out=None, max_prefix=None,
               max_token_text_ratio=20, min_token_text_ratio=2, pace=None, mixed_sampling=False, win_cap=None, mixed_heads=False, head_cap=None,
-              stream=False, sync_every=None, event_log=None, incremental_vocoder=False):
+              stream=False, sync_every=None, event_log=None, incremental_vocoder=False, incremental_flow=False):
         """The continuous engine over an open-ended SOURCE of utterances: `source.poll(block)` returns the next `Utterance`, or None when
         nothing is waiting (it is asked to block only while the decode grid is idle), and raises StopIteration when closed.  Generator over
         (utterance, waveform | exception, tokens) in completion order.
@@ -386,6 +398,10 @@ class HvxPipeline:
         piece is vocoded from a window of the cache — left context + new frames + look-ahead — instead of the whole cache; pieces, order, `index` and `final`
         are those of the switch-off path.  The stream is released with the plane (final piece, cancel, drop, abandoned).  `last_continuous['vocoder_frames']`:
         mel frames the vocoder decoded over the call, with the switch on or off.
+        `incremental_flow` (with `stream`; ValueError without; independent of `incremental_vocoder`): every utterance owns a flow stream (flow.FlowStream) and a non-final
+        chunk job solves only the rows from the last chunk boundary at or below the frames already handed out, against the cached keys and values of the rows below
+        (HvxFlow.solve_incremental_batch); such jobs are bucketed by window length instead of prefix length.  Final jobs (full mask) are whole-prefix solves, as with the
+        switch off.  The stream is released with the plane.  `last_continuous['flow_rows']`: rows the flow solved over the call, window or prefix, with the switch on or off.
         `sync_every`: decode steps per host round trip of the grid (default 8); smaller: tokens — and so pieces — surface at a finer cadence, for more
         round trips.
         Cancelling ONE utterance: `Utterance.cancel` (any object with is_set()) goes to the decode engine with the request (HvxLLM.generate_stream).  Unstreamed, a
@@ -397,6 +413,8 @@ class HvxPipeline:
         piecewise = bool(stream)                           # (`stream` names the acoustic stage's device stream below)
         if incremental_vocoder and not piecewise:
             raise ValueError('incremental_vocoder needs stream=True: an unstreamed utterance is vocoded once')
+        if incremental_flow and not piecewise:
+            raise ValueError('incremental_flow needs stream=True: an unstreamed utterance is solved once')
         import queue
         import threading
         if getattr(self, '_bg_stream', None) is None:
@@ -443,7 +461,7 @@ class HvxPipeline:
         fetched = {}                                       # stream: running id -> (time of its fetch, tokens its mel cache must hold), until its session exists
         live = {}                                          # stream: running id -> _StreamUtterance, until its final piece has left
         acct = dict(pieces=0, chunk_solves=0, first=deque(maxlen=4096), acoustic=0.0, audio=0.0, tokens=0, cancelled=0, with_cancel=False, vocoder_frames=0,
-                    incremental=bool(incremental_vocoder))
+                    incremental=bool(incremental_vocoder), incremental_flow=bool(incremental_flow), flow_rows=0)
 
         class _Requests:
             @staticmethod
@@ -580,7 +598,7 @@ class HvxPipeline:
                 for se in live.values():                            # (utterances the run leaves behind: abandoned, or cut off by an error)
                     se.release()
                 self.last_continuous.update(tokens=acct['tokens'], audio_seconds=acct['audio'], acoustic_seconds=acct['acoustic'], pieces=acct['pieces'],
-                                            chunk_solves=acct['chunk_solves'], first_piece_seconds=list(acct['first']), vocoder_frames=acct['vocoder_frames'],
+                                            chunk_solves=acct['chunk_solves'], first_piece_seconds=list(acct['first']), vocoder_frames=acct['vocoder_frames'], flow_rows=acct['flow_rows'],
                                             pieces_out=[0] * len(abandoned) + [live[k].pieces if k in live else 0 for k in seen])
 
     def _stream_consumer(self, q, seen, fetched, live, flow, hift, stream, acoustic_batch, acct, event_log, max_pad=0.15):
@@ -596,7 +614,8 @@ class HvxPipeline:
             if n not in live:
                 t_fetch, budget = fetched.pop(n)
                 with _on(stream):                                  # (its copies to the device are ordered with the solves that read them)
-                    live[n] = _StreamUtterance(seen[n], flow, hop, budget, self.device, t_fetch, hift=hift if acct['incremental'] else None)
+                    live[n] = _StreamUtterance(seen[n], flow, hop, budget, self.device, t_fetch, hift=hift if acct['incremental'] else None,
+                                               **(dict(incremental_flow=True) if acct['incremental_flow'] else {}))
             return live[n]
 
         def drop(n):
@@ -678,15 +697,24 @@ class HvxPipeline:
             out = []
             with _on(stream):
                 for final in (False, True):                        # a final job runs with the full mask: its own solves
-                    todo = sorted((n for n in picked if jobs[n][2] == final), key=lambda n: -(live[n].n_prompt + jobs[n][0]))
+                    windowed = acct['incremental_flow'] and not final       # non-final jobs solve windows: bucketed by window length instead of prefix length
+                    size = (lambda n: live[n].window_rows(flow, jobs[n][0], jobs[n][1])) if windowed else (lambda n: live[n].n_prompt + jobs[n][0])
+                    todo = sorted((n for n in picked if jobs[n][2] == final), key=lambda n: -size(n))
                     while todo:
-                        top = live[todo[0]].n_prompt + jobs[todo[0]][0]
-                        bucket = [n for n in todo if live[n].n_prompt + jobs[n][0] >= (1.0 - max_pad) * top]
+                        top = size(todo[0])
+                        bucket = [n for n in todo if size(n) >= (1.0 - max_pad) * top]
                         todo = [n for n in todo if n not in bucket]
                         ins = [live[n].flow_inputs(flow, jobs[n][0], final) for n in bucket]
-                        fresh = flow.solve_stream_batch([i[0] for i in ins], [i[1] for i in ins], [i[2] for i in ins],
-                                                        [live[n].prompt_frames + jobs[n][1] * ratio for n in bucket], [live[n].cache for n in bucket],
-                                                        [live[n].fill for n in bucket], streaming=not final)
+                        if windowed:
+                            acct['flow_rows'] += sum(size(n) for n in bucket)
+                            fresh = flow.solve_incremental_batch([live[n].fstream for n in bucket], [i[0] for i in ins], [i[1] for i in ins], [i[2] for i in ins],
+                                                                 [live[n].prompt_frames + jobs[n][1] * ratio for n in bucket], [live[n].cache for n in bucket],
+                                                                 [live[n].fill for n in bucket])
+                        else:
+                            acct['flow_rows'] += sum(int(i[0].shape[-1]) for i in ins)
+                            fresh = flow.solve_stream_batch([i[0] for i in ins], [i[1] for i in ins], [i[2] for i in ins],
+                                                            [live[n].prompt_frames + jobs[n][1] * ratio for n in bucket], [live[n].cache for n in bucket],
+                                                            [live[n].fill for n in bucket], streaming=not final)
                         acct['chunk_solves'] += 1
                         for n, f in zip(bucket, fresh):
                             se = live[n]

@@ -18,12 +18,18 @@ class StreamSession:
     been handed to the caller.  Every push = flow over the token prefix -> keep only the frames past the prefix already covered ->
     vocode ALL frames so far -> return the samples not yet handed out."""
 
-    def __init__(self, flow, hift, prompt_token, prompt_feat, embedding, device=None, incremental_vocoder=False, max_frames=None):
+    def __init__(self, flow, hift, prompt_token, prompt_feat, embedding, device=None, incremental_vocoder=False, max_frames=None, incremental_flow=False):
         """incremental_vocoder: the session owns a vocoder stream (`hift.stream(max_frames)`, hift.HiftStream) and every push vocodes a window of the
         cached mel — left context + new frames + look-ahead — instead of all of it; the samples are those of the whole-cache pass.  max_frames:
         the longest utterance the stream holds (default: what the vocoder's fixed noise table covers, `hift.max_stream_frames`).  The stream is
-        released with the final push (or close())."""
+        released with the final push (or close()).
+        incremental_flow: the session owns a flow stream (`flow.stream(max_frames)`, flow.FlowStream — here max_frames counts the prompt's frames too and defaults to
+        the flow's max_t) and every non-final push solves only the rows from the last chunk boundary at or below the frames already handed out, against the cached keys
+        and values of the rows below (HvxFlow.solve_incremental_batch); the final push — full mask — stays a whole-prefix solve.  `flow_rows` counts the rows solved,
+        with the switch on or off."""
         self.flow, self.hift = flow, hift
+        self._fstream = flow.stream(int(max_frames) if max_frames is not None else flow.max_t) if incremental_flow else None
+        self.flow_rows = 0
         self._vstream = hift.stream(int(max_frames) if max_frames is not None else hift.max_stream_frames) if incremental_vocoder else None
         self.device = device if device is not None else getattr(flow, 'device', 'cpu')
         self.embedding = embedding.to(self.device)
@@ -38,9 +44,29 @@ class StreamSession:
 
     def _fresh_frames(self, token, covered, stream, finalize):
         """mel frames of the tokens past the first `covered` ones (the flow re-runs over the whole prefix, as the reference does)"""
+        ratio = self.flow.token_mel_ratio
+        n_prompt = self._prompt['prompt_token'].shape[1] if self._prompt else 0
+        if self._fstream is not None and stream and not finalize:
+            tok = token.to(self.device, dtype=torch.int32).reshape(-1)
+            prompt_frames = 0
+            if self._prompt:
+                tok = torch.concat([self._prompt['prompt_token'].reshape(-1).to(torch.int32), tok])
+                prompt_frames = int(self._prompt['prompt_feat'].shape[1])
+            mu, spk = self.flow.encode(tok, self.embedding.reshape(-1), finalize=False)
+            T = int(mu.shape[-1])
+            cond = torch.zeros(mu.shape[0], T, dtype=torch.float32, device=mu.device)
+            if prompt_frames:
+                cond[:, :prompt_frames] = self._prompt['prompt_feat'][0].to(mu.device, torch.float32).t()
+            done = prompt_frames + covered * ratio
+            plane = torch.empty(mu.shape[0], T - done, dtype=torch.float32, device=mu.device)
+            before = self._fstream.rows_solved
+            self.flow.solve_incremental_batch([self._fstream], [mu], [spk], [cond], [done], [plane], [0])
+            self.flow_rows += self._fstream.rows_solved - before
+            return plane.unsqueeze(0)
         mel, _ = self.flow.inference(token=token.to(self.device, dtype=torch.int32), token_len=torch.tensor([token.shape[1]], dtype=torch.int32),
                                      embedding=self.embedding, streaming=stream, finalize=finalize, **self._prompt)
-        return mel[:, :, covered * self.flow.token_mel_ratio:]
+        self.flow_rows += ratio * (n_prompt + int(token.shape[1]) - (0 if finalize else self.flow.pre_lookahead_len))
+        return mel[:, :, covered * ratio:]
 
     def _unheard(self, wav):
         out = wav[:, self._handed:]
@@ -65,13 +91,19 @@ class StreamSession:
                 self.close()
             return out
         wav, _ = self.hift.inference(speech_feat=mel, finalize=finalize)
+        if finalize and self._fstream is not None:          # (the flow stream goes with the utterance's last piece)
+            self._fstream.release()
+            self._fstream = None
         return self._unheard(wav)
 
     def close(self):
-        """release the vocoder stream (the final push does it; a session that is abandoned earlier calls this)"""
+        """release the vocoder and flow streams (the final push does it; a session that is abandoned earlier calls this)"""
         if self._vstream is not None:
             self._vstream.close()
             self._vstream = None
+        if self._fstream is not None:
+            self._fstream.release()
+            self._fstream = None
 
     # the reference's name and argument order (cli/model.py:405)
     def token2wav(self, token, token_offset, stream=False, finalize=False, speed=1.0):
@@ -113,7 +145,8 @@ class ChunkSchedule:
         return len(self.tokens), self.covered
 
 
-def stream_tts(token_source, flow, hift, prompt_token, prompt_feat, embedding, token_hop_len=25, stream=True, speed=1.0, incremental_vocoder=False):
+def stream_tts(token_source, flow, hift, prompt_token, prompt_feat, embedding, token_hop_len=25, stream=True, speed=1.0, incremental_vocoder=False,
+               incremental_flow=False):
     """Generator of waveform pieces (1, L) float32 from an iterable of speech-token ids (e.g. `HvxLLM.inference(...)`).
 
     The chunk schedule is the reference's (cli/model.py:329-352), kept in `ChunkSchedule`: the first hop is padded so that prompt + hop is a whole number
@@ -122,10 +155,14 @@ def stream_tts(token_source, flow, hift, prompt_token, prompt_feat, embedding, t
     `static_chunk_size / token_mel_ratio` ("must matching training static_chunk_size", cli/model.py:395-396).
     incremental_vocoder: every piece is vocoded from a window of the mel cache and the session's vocoder stream (StreamSession); same pieces.  It
     needs stream=True (ValueError otherwise: an unstreamed utterance is vocoded once).
+    incremental_flow: every non-final piece's flow solves a window against the session's flow stream (StreamSession) instead of the whole prefix.  Independent of
+    incremental_vocoder; needs stream=True too (ValueError otherwise: an unstreamed utterance is solved once).
     """
     if incremental_vocoder and not stream:
         raise ValueError('incremental_vocoder needs stream=True: an unstreamed utterance is vocoded once')
-    sess = StreamSession(flow, hift, prompt_token, prompt_feat, embedding, incremental_vocoder=incremental_vocoder)
+    if incremental_flow and not stream:
+        raise ValueError('incremental_flow needs stream=True: an unstreamed utterance is solved once')
+    sess = StreamSession(flow, hift, prompt_token, prompt_feat, embedding, incremental_vocoder=incremental_vocoder, incremental_flow=incremental_flow)
     try:
         yield from _stream_tts(sess, token_source, flow, prompt_token, token_hop_len, stream, speed)
     finally:

@@ -390,7 +390,8 @@ class _TaskSource:
 
 
 def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_id, frontend_factory=None, lm_slots=None, acoustic_batch=4,
-                               mixed_sampling=False, mixed_heads=False, stream=False, segment_fanout=False, incremental_vocoder=False):
+                               mixed_sampling=False, mixed_heads=False, stream=False, segment_fanout=False, incremental_vocoder=False,
+                               incremental_flow=False):
     """Same wire format as worker_process_tts, served by the continuous-batching engine (replaces the one-request-at-a-time
     loop of server/worker.py:54-102 and what server/router.py:144-156 feeds it): `tts` / `zero_shot` tasks join ONE decode grid as they arrive
     (HvxPipeline.serve -> HvxLLM.generate_stream: the LM weights are streamed once per step for every request in flight, a finished request's
@@ -402,6 +403,7 @@ def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_
     mixed_heads=True: requests with different inference_head_num share the grid as well (rows per sequence: the model's head_num).
     stream=True: one result message per audio PIECE (see serve_queue).
     incremental_vocoder=True (with stream=True): the pieces come from a per-request vocoder stream instead of a pass over the whole mel cache (see serve_queue).
+    incremental_flow=True (with stream=True): non-final pieces solve a window of the flow against per-request K / V caches instead of the whole prefix (see serve_queue).
     segment_fanout=True: a `tts` task over 5000 characters no longer drains the grid: its segments are utterances of the running epoch (see serve_queue)."""
     os.environ['CUDA_VISIBLE_DEVICES'] = str(worker_id % num_workers_gpu)
     from .model_manager import HvxModelManager
@@ -413,11 +415,11 @@ def worker_process_tts_batched(num_workers_gpu, task_queue, result_dict, worker_
                                       fp16=_env_flag('TTS_FP_16'), cpu=_env_flag('TTS_CPU', False)))
     serve_queue(mm, task_queue, result_dict, worker_id, lm_slots=lm_slots, acoustic_batch=acoustic_batch, mixed_sampling=mixed_sampling,
                 mixed_heads=mixed_heads, **(dict(stream=True) if stream else {}), **(dict(segment_fanout=True) if segment_fanout else {}),
-                **(dict(incremental_vocoder=True) if incremental_vocoder else {}))
+                **(dict(incremental_vocoder=True) if incremental_vocoder else {}), **(dict(incremental_flow=True) if incremental_flow else {}))
 
 
 def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acoustic_batch=4, normalise=None, mixed_sampling=False, win_cap=64, token_log=None,
-                mixed_heads=False, head_cap=None, stream=False, segment_fanout=False, segmented_text_chars=None, incremental_vocoder=False):
+                mixed_heads=False, head_cap=None, stream=False, segment_fanout=False, segmented_text_chars=None, incremental_vocoder=False, incremental_flow=False):
     """the loop of worker_process_tts_batched over an already loaded model manager (tests drive this directly).  Returns its counters:
     `epochs` (decode grids started) and `epoch_boundaries` (tasks that closed a running grid because they could not join it; the shutdown
     sentinel is not one).  token_log: a dict that receives task id -> speech-token ids of every synthesised request.
@@ -427,6 +429,8 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
     `piece_index` and `final`.  A request that fails is answered once, under its task id, as without the switch.
     incremental_vocoder=True: HvxPipeline.serve(stream=True, incremental_vocoder=True) — same messages, the vocoder works on a window per piece (hift.HiftStream);
     without stream=True it is refused with a ValueError before anything is served.
+    incremental_flow=True: HvxPipeline.serve(stream=True, incremental_flow=True) — same messages, non-final pieces solve a window of the flow (flow.FlowStream); refused
+    without stream=True in the same way; independent of incremental_vocoder.
     segment_fanout=True: a `tts` task over `segmented_text_chars` characters (None: model_manager.SEGMENTED_TEXT_CHARS) that can join an epoch is served as
     its segments in the decode grid (_TaskSource) instead of one by one between two epochs.  When the last segment has its waveform, ONE result is written
     under the task id: the keys of text_to_speech's segmented result, `output_audio` = the segments in text order with the zero gaps between them.  The first
@@ -439,6 +443,8 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
     from collections import deque
     if incremental_vocoder and not stream:
         raise ValueError('incremental_vocoder needs stream=True: an unstreamed request is vocoded once')
+    if incremental_flow and not stream:
+        raise ValueError('incremental_flow needs stream=True: an unstreamed request is solved once')
     stats = dict(epochs=0, epoch_boundaries=0, mixed_sampling=bool(mixed_sampling), mixed_heads=bool(mixed_heads), fanned_out=0, cancelled=0)
     backlog = deque()                                  # the one task a source read past while segments were waiting (it was looking for cancel tasks): served before the queue
     fan_kw = dict(segment_fanout=bool(segment_fanout), segmented_text_chars=segmented_text_chars, backlog=backlog)
@@ -487,6 +493,8 @@ def serve_queue(mm, task_queue, result_dict, worker_id=0, lm_slots=None, acousti
                 kw.update(stream=True)
             if incremental_vocoder:
                 kw.update(incremental_vocoder=True)
+            if incremental_flow:
+                kw.update(incremental_flow=True)
             for u, wav, toks in pipe.serve(_Tracked(src, in_flight), lm_slots=lm_slots, acoustic_batch=acoustic_batch, acoustic_min_batch=1, **kw):
                 t = u.tag
                 if getattr(u, 'segment', None) is not None:     # a segment of a fanned-out task

@@ -459,6 +459,63 @@ int hvx_cfm_solve_stream_batch(hvx_flow* h, hvx_stream s, void* ws, size_t ws_by
 int hvx_op_mel_cache_append(const float* x, int32_t n, int32_t mel, int32_t t_max, const int32_t* t_len, const int32_t* covered, float* const* cache,
                             const int32_t* cache_ld, const int32_t* cache_fill, hvx_stream s);
 
+/* ---- Incremental streaming flow (still ABI 8, additive) ------------------------------------------------------------------------------------------
+ * With the static chunk mask the estimator is causal by chunk: row r sees keys j < (r / chunk + 1) * chunk and nothing else of the model looks ahead (causal
+ * convolutions, per-row norms and Linears, RoPE by absolute position, fixed noise, final mu rows).  A later, longer prefix therefore repeats — at every Euler step, block
+ * and CFG branch — the x-trajectory and the K / V of every row below the last chunk boundary of the earlier prefix.  hvx_cfm_solve_incremental_batch keeps them: a job of T
+ * frames with `covered` frames handed out computes rows [r0, T) only, r0 = covered / chunk * chunk, against the cached keys and values of rows [0, r0).
+ * The per-utterance STATE is caller memory (device, 16-byte aligned) of hvx_flow_stream_state_bytes(h, max_frames, n_steps) bytes, cap = max_frames rounded up to 64:
+ *     for every (step, block, branch): K [heads][cap][64], then V^T [heads][64][cap], in the attention's operand type (bf16 handles: bf16, fp32 handles: fp32)
+ *     the x-trajectory [n_steps][mel][cap] fp32 (x as it enters each step: the left context of the two causal position-embedding convolutions)
+ * = n_steps * depth * 2 * 2 * heads * cap * 64 * sizeof(operand) + n_steps * mel * cap * 4 bytes: 1.76 MB per frame at CV3 dimensions in bf16, 3.6 GB at max_frames 2048.
+ * The host side of a state (its capacity, schedule, chunk size and `fill`, the length of the last prefix) lives in the flow handle, keyed by the state's address:
+ * _bind registers it (host only, nothing is launched), _reset zero-fills it on the stream (a new utterance in the same memory; padded key columns must be finite) and
+ * sets fill = 0, _info reads out[4] = {cap, n_steps, chunk, fill}, _release forgets it.  A bound state needs one _reset before its first job. */
+size_t hvx_flow_stream_state_bytes(const hvx_flow* h, int32_t max_frames, int32_t n_steps);
+size_t hvx_flow_stream_workspace_bytes(const hvx_flow* h, int32_t n, int32_t window);      /* n sessions whose longest window T - r0 is `window` rows */
+int hvx_flow_stream_bind(hvx_flow* h, void* state, size_t state_bytes, int32_t max_frames, int32_t n_steps, const float* t_steps, int32_t static_chunk_size);
+int hvx_flow_stream_reset(hvx_flow* h, hvx_stream s, void* state);
+int hvx_flow_stream_info(hvx_flow* h, const void* state, int32_t* out);
+/* the caller vouches that the state's memory holds a solved prefix of `fill` frames — a copy of another utterance's state over the same prompt and tokens, a state
+ * restored from elsewhere; 0 empties it without the zero-fill.  Host only. */
+int hvx_flow_stream_set_fill(hvx_flow* h, const void* state, int32_t fill);
+int hvx_flow_stream_release(hvx_flow* h, const void* state);
+/* hvx_cfm_solve_stream_batch's arguments (x, mu, cond: the WHOLE prefixes, (n, mel, t_max), x holding the noise; t_len, covered, cache_ld, cache_fill: HOST int32 [n]; cache:
+ * HOST array of n planes) plus states: HOST array of n bound states.  n <= 16.  Frames [covered[i], t_len[i]) of x[i] are the new mel frames on return and are appended to
+ * cache[i] as hvx_cfm_solve_stream_batch appends them; rows [r0, covered) are recomputed and dropped, rows below r0 of x are not touched.  A session whose state is empty (fill == 0:
+ * its first job, r0 = 0 whatever `covered` says — a prompt's frames are covered from the start) or whose r0 is 0 is solved whole, which fills its state.  Refused with -1 before anything is launched or any state is touched: a null argument, a state that is not
+ * bound, covered > fill (fill > 0), t_len <= covered, t_len > cap or t_max, a schedule (n_steps, t_steps compared bitwise) or chunk size other than the state's, static_chunk_size
+ * == 0 (an utterance's final job runs with the full mask: it stays a whole-prefix solve, one O(T^2) solve per utterance), an fp16-mode handle, what
+ * hvx_cfm_solve_stream_batch refuses of the cache planes.  Workspace: hvx_flow_stream_workspace_bytes. */
+int hvx_cfm_solve_incremental_batch(hvx_flow* h, hvx_stream s, void* ws, size_t ws_bytes, int32_t n, int32_t t_max, void* const* states, const int32_t* t_len, float* x,
+                                    const float* mu, const float* spks, const float* cond, int32_t n_steps, const float* t_steps, const float* dt_steps,
+                                    int32_t static_chunk_size, const int32_t* covered, float* const* cache, const int32_t* cache_ld, const int32_t* cache_fill);
+
+/* The windowed DiT attention of that solve: `rows` query rows per (batch entry, head) — rows r0[b] .. r0[b] + rows - 1 of their sequence — against kv_len[b] keys of cache
+ * slot kv_slot[b].  q [batch][heads][q_pad][64] (window-local rows); k [slot][heads][cap][64] and vT [slot][heads][64][cap] with slot_stride elements between slots, cap %
+ * 64 == 0; out [batch][rows][heads * 64].  Row i of entry b sees keys j < min(kv_len[b], ((r0[b] + i) / chunk + 1) * chunk) (chunk <= 0: all kv_len[b]).  kv_slot, r0,
+ * kv_len: optional DEVICE int32 [batch] (absent: slot b, r0_const, kv_max); kv_max: the longest kv_len, <= cap.  The keys are split over workgroups (split_chunk keys each,
+ * a multiple of 64; 0: chosen from the shape, at most max_splits) and the partials combined: part_o f32 [batch][heads][max_splits][rows_pad][64], part_ml [..][rows_pad][2],
+ * rows_pad = rows rounded up to 32.  Cache contents at or beyond kv_len[b] must be finite.  bf16: a flash-decoding shaped kernel (csrc/attention.hip:
+ * attn_window_kernel); fp32: the generic kernel with key splits. */
+typedef struct {
+    int32_t dtype, batch, heads, rows, q_pad;
+    const void* q; void* out;
+    const void* k; const void* vT; int32_t cap; int64_t slot_stride;
+    const int32_t* kv_slot; const int32_t* r0; const int32_t* kv_len;
+    int32_t r0_const, kv_max, chunk;
+    float scale; int32_t q_log2;
+    int32_t split_chunk, max_splits; float* part_o; float* part_ml;
+} hvx_attn_window_args;
+int hvx_op_attention_window(const hvx_attn_window_args* a, hvx_stream s);
+/* the split count that launch chooses (split_chunk 0), and through *split_chunk its split length; host arithmetic */
+int hvx_op_attention_window_splits(int32_t dtype, int32_t batch, int32_t heads, int32_t rows, int32_t kv_max, int32_t max_splits, int32_t* split_chunk);
+/* The cache append of that solve: window K [2 n][heads][t_pad][64] and V^T [2 n][heads][64][t_pad] (entry 2 i + branch, `es` bytes per element: 2 or 4) -> rows /
+ * columns [r0[i], r0[i] + rows[i]) of session i's caches dk[i] [heads][cap[i]][64] and dv[i] [heads][64][cap[i]] (branch 1: branch_stride[i] elements behind).  Host
+ * arrays, n <= 16; rows that would leave a cache are refused before the launch. */
+int hvx_op_kv_window_append(const void* k, const void* vT, int32_t es, int32_t heads, int32_t t_pad, int32_t n, void* const* dk, void* const* dv,
+                            const int64_t* branch_stride, const int32_t* cap, const int32_t* r0, const int32_t* rows, hvx_stream s);
+
 /* ---------------------------------------------------------------------------------------------------
  * HiFT — replaces CausalHiFTGenerator.inference / decode (cosyvoice/hifigan/generator.py:713-726, 672-711),
  * CausalConvRNNF0Predictor.forward (cosyvoice/hifigan/f0_predictor.py:95-103), SourceModuleHnNSF / SineGen2

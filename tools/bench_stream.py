@@ -8,6 +8,9 @@ Prints time to first audio and the arrival time / length of every piece; full-si
                                                                        # with stream=False (what streaming costs under load)
     python tools/bench_stream.py --incremental-vocoder [--serve 8 --slots 8]   # the vocoder on a window per piece (hift.HiftStream) against the whole-cache pass, both
                                                                        # settings in this process: per-piece arrival times, acoustic seconds, vocoder_frames
+    python tools/bench_stream.py --incremental-flow [--serve 8 --slots 8]      # the flow on a window per non-final piece against cached K / V (flow.FlowStream) against the
+                                                                       # whole-prefix solve, both settings in this process: device time per piece, acoustic seconds,
+                                                                       # flow_rows (profiles/flow_stream_ab.log)
 """
 import argparse
 import os
@@ -40,8 +43,8 @@ def serve_bench(a):
         def poll(self, block):
             return next(self.it)
     kw = dict(lm_slots=a.slots, max_out=n_spk, max_prefix=2 + a.chars + 20 + a.prompt, **(dict(sync_every=a.sync_every) if a.sync_every else {}))
-    if a.incremental_vocoder:
-        return serve_ab(a, cfg, pipe, Src, kw, n_spk)
+    if a.incremental_vocoder or a.incremental_flow:
+        return serve_ab(a, cfg, pipe, Src, kw, n_spk, 'incremental_flow' if a.incremental_flow else 'incremental_vocoder')
     for rep in range(2):                                        # first pass warms up (graph capture, workspaces)
         torch.cuda.synchronize()
         t0 = time.time()
@@ -76,30 +79,65 @@ def serve_bench(a):
               % (plain['tokens'], t_plain, plain['tokens'] / t_plain, (lc['tokens'] / t_stream) / (plain['tokens'] / t_plain)))
 
 
-def serve_ab(a, cfg, pipe, Src, kw, n_spk):
-    """serve(stream=True) with incremental_vocoder off and on, same requests, one process: arrival time of every piece, acoustic seconds, vocoder_frames"""
+def serve_ab(a, cfg, pipe, Src, kw, n_spk, switch='incremental_vocoder'):
+    """serve(stream=True) with `switch` off and on, same requests, one process: arrival time of every piece, acoustic seconds, vocoder_frames, flow_rows"""
     res = {}
     for rep in range(2):                                        # first pass warms up (graph capture, workspaces)
         for on in (False, True):
             torch.cuda.synchronize()
             t0 = time.time()
             arr = {}
-            for u, piece, info in pipe.serve(Src(), stream=True, incremental_vocoder=on, **kw):
+            for u, piece, info in pipe.serve(Src(), stream=True, **{switch: on}, **kw):
                 if isinstance(piece, BaseException):
                     raise piece
                 piece = piece.cpu()
                 arr.setdefault(u.seed, []).append(time.time() - t0)
             res[on] = (arr, time.time() - t0, dict(pipe.last_continuous))
-    print('serve A/B: %d requests of %d tokens in %d slots; incremental_vocoder off | on' % (a.serve, n_spk, a.slots))
+    print('serve A/B: %d requests of %d tokens in %d slots; %s off | on' % (a.serve, n_spk, a.slots, switch))
     for on in (False, True):
         arr, t, lc = res[on]
-        print('  %s: %d pieces, %.3f s wall, acoustic %.3f s, vocoder_frames %d, audio %.2f s, %.0f tokens/s'
-              % ('on ' if on else 'off', lc['pieces'], t, lc['acoustic_seconds'], lc['vocoder_frames'], lc['audio_seconds'], lc['tokens'] / t))
+        print('  %s: %d pieces, %.3f s wall, acoustic %.3f s, vocoder_frames %d, flow_rows %d, audio %.2f s, %.0f tokens/s'
+              % ('on ' if on else 'off', lc['pieces'], t, lc['acoustic_seconds'], lc['vocoder_frames'], lc['flow_rows'], lc['audio_seconds'], lc['tokens'] / t))
     for seed in sorted(res[False][0]):
         print('  request %d piece arrival [s] off: %s' % (seed, ' '.join('%.3f' % x for x in res[False][0][seed])))
         print('  request %d piece arrival [s] on : %s' % (seed, ' '.join('%.3f' % x for x in res[True][0][seed])))
-    print('  acoustic seconds on / off = %.3f; vocoder_frames on / off = %.3f'
-          % (res[True][2]['acoustic_seconds'] / res[False][2]['acoustic_seconds'], res[True][2]['vocoder_frames'] / float(res[False][2]['vocoder_frames'])))
+    print('  acoustic seconds on / off = %.3f; vocoder_frames on / off = %.3f; flow_rows on / off = %.3f'
+          % (res[True][2]['acoustic_seconds'] / res[False][2]['acoustic_seconds'], res[True][2]['vocoder_frames'] / float(res[False][2]['vocoder_frames']),
+             res[True][2]['flow_rows'] / float(res[False][2]['flow_rows'])))
+
+
+def flow_ab(a, cfg, pipe):
+    """the flow alone over one utterance's chunk jobs (prompt + hops of `static_chunk_size` frames, the final full-mask job left out: it is the same solve in both
+    settings): device time per piece, whole-prefix solve against FlowStream (random mu: the arithmetic does not depend on the values)"""
+    flow, hop = pipe.flow, cfg.flow.static_chunk_size
+    prompt = -(-2 * a.prompt // hop) * hop                      # the schedule pads prompt + first hop to whole chunks
+    n = prompt + 2 * int(a.chars * 5.5) // hop * hop
+    g = torch.Generator().manual_seed(0)
+    mu, cond, spk = torch.randn(80, n, generator=g).to('cuda'), torch.zeros(80, n, device='cuda'), torch.randn(80, generator=g).to('cuda')
+    jobs = [(T, max(T - hop, prompt) if T > prompt + hop else prompt) for T in range(prompt + hop, n + 1, hop)]
+    out = {}
+    for on in (False, True):
+        for rep in range(2):
+            st = flow.stream(n) if on else None
+            plane = torch.empty(80, n, device='cuda')
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(jobs) + 1)]
+            ev[0].record()
+            fill = 0
+            for i, (T, cov) in enumerate(jobs):
+                if on:
+                    fill += flow.solve_incremental_batch([st], [mu[:, :T]], [spk], [cond[:, :T]], [cov], [plane], [fill])[0]
+                else:
+                    fill += flow.solve_stream_batch([mu[:, :T]], [spk], [cond[:, :T]], [cov], [plane], [fill], streaming=True)[0]
+                ev[i + 1].record()
+            torch.cuda.synchronize()
+            out[on] = ([ev[i].elapsed_time(ev[i + 1]) for i in range(len(jobs))], st.rows_solved if on else sum(T for T, _ in jobs))
+            if on:
+                st.release()
+    print('flow alone: %d frames (%d of them prompt) in %d non-final pieces of %d' % (n, prompt, len(jobs), hop))
+    for on in (False, True):
+        ms, rows = out[on]
+        print('  %s: %.2f ms in all, rows solved %d; per piece [ms]: %s' % ('on ' if on else 'off', sum(ms), rows, ' '.join('%.2f' % x for x in ms)))
+    print('  time on / off = %.3f; last piece on / off = %.3f' % (sum(out[True][0]) / sum(out[False][0]), out[True][0][-1] / out[False][0][-1]))
 
 
 def vocoder_ab(a, cfg, pipe):
@@ -141,6 +179,7 @@ def main():
     ap.add_argument('--slots', type=int, default=8, help='decode-grid slots of --serve')
     ap.add_argument('--sync-every', type=int, default=None, help='decode steps per host round trip of --serve (default 8)')
     ap.add_argument('--incremental-vocoder', action='store_true', help='A/B of the windowed vocoder (hift.HiftStream) against the whole-cache pass, in one process')
+    ap.add_argument('--incremental-flow', action='store_true', help='A/B of the windowed flow (flow.FlowStream) against the whole-prefix solve, in one process')
     a = ap.parse_args()
     if a.serve:
         return serve_bench(a)
@@ -164,13 +203,16 @@ def main():
 
     if a.incremental_vocoder:
         vocoder_ab(a, cfg, pipe)
+    if a.incremental_flow:
+        flow_ab(a, cfg, pipe)
     for rep in range(2):                                        # first pass warms up (graph capture, workspaces)
-        for stream, inc in ((True, False), (True, True), (False, False)) if a.incremental_vocoder else ((True, False), (False, False)):
+        for stream, inc in ((True, False), (True, True), (False, False)) if (a.incremental_vocoder or a.incremental_flow) else ((True, False), (False, False)):
             torch.cuda.synchronize()
             t0 = time.time()
             arr = []
             for wav in stream_tts(tokens(), pipe.flow, pipe.hift, u.prompt_speech_token[None], u.prompt_feat[None], u.embedding[None],
-                                  token_hop_len=cfg.flow.static_chunk_size // cfg.flow.token_mel_ratio, stream=stream, **(dict(incremental_vocoder=True) if inc else {})):
+                                  token_hop_len=cfg.flow.static_chunk_size // cfg.flow.token_mel_ratio, stream=stream,
+                                  **({'incremental_flow' if a.incremental_flow else 'incremental_vocoder': True} if inc else {})):
                 wav = wav.cpu()
                 arr.append((time.time() - t0, wav.shape[1] / cfg.sample_rate))
             if rep == 0:
